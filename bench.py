@@ -15,7 +15,12 @@ and exits with its status; every rank checks WORLD_SIZE == --gpus.  Events are s
 by eventNum % world (weak scaling, no data-path collective); `--landing spread` adds the
 route + all-to-all-v exchange of config 4.
 
-A second, separately reported leg (`reas_cold`) times the receive side alone on
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and no
+more: it sets up, warms up, times the K steps, writes the last step's outputs if
+`--dump-outputs DIR` is given, and prints the line.  `--full` adds everything else, each
+outside the timed region: the byte-exact round-trip verification, the per-kernel roofline
+pass and copy calibration, the sub-legs (`--subs`), the CPU baseline and a second,
+separately reported leg (`reas_cold`) that times the receive side alone on
 datagrams written long before (every batch in its own buffer, 1.1 GB in all, so each
 launch reads them back from HBM, not from the Infinity Cache): the real receive path.
 
@@ -116,6 +121,15 @@ def parse(argv=None):
                          "MTU 9000 half (1 MiB events), BASELINE config 3 (8 MiB events at MTU 9000, 70 "
                          "events = 65,730 datagrams per launch) and BASELINE config 4 (datagrams landing "
                          "spread over the ranks, exchanged over RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the byte-exact round-trip "
+                         "verification, the per-kernel roofline pass with its copy calibration, the cold "
+                         "receive leg (--cold-steps), the sub-legs (--subs) and the CPU baseline "
+                         "(--cpu-seconds).  Without it the run sets up, warms up, times --steps steps and "
+                         "prints the line; those options then have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, under 64 MB in all; see dump_outputs)")
     ap.add_argument("--quiet", action="store_true")
     return ap.parse_args(argv)
 
@@ -328,6 +342,74 @@ def copy_calibration(ctx, torch, dev):
     return best, per
 
 
+DUMP_SEED = 0xD0E25A
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, torch, arena, recs, B, packets, lens, stride, n_packets):
+    """--dump-outputs: what the last timed step left for its caller, as float32 / float64
+    .npy files under out_dir (rank 0's, 64 MB in all at the most), so that two builds can be
+    compared output for output.  Events are taken in eventNum order (where an event lies in
+    the arena is the reassembler's business), positions and rows are fixed by DUMP_SEED:
+
+      records.npy            (E, 4) f64  eventNum, bytes, dataId, numFragments per completed event
+      event_sums.npy         (E, 2) f64  per event, over all its bytes b[i]: sum b[i] and
+                                         sum b[i] * (i % 65521 + 1), both exact in float64
+      events_sample.npy      (E, P) f32  per event, its bytes at P sampled positions (first and last among them)
+      events_sample_pos.npy  (P,)   f64  those positions
+      events_head.npy        (4, H) f32  four sampled events, their first H = min(B, 1 MiB) bytes
+      events_head_idx.npy    (4,)   f64  their rows in records.npy
+      datagrams_sample.npy   (D, stride) f32  sampled datagram slots of the step's last batch,
+                                         zero past each datagram's length
+      datagrams_sample_idx.npy (D,) f64  their indices in that batch
+      datagram_lengths.npy   (n,)   f32  every datagram length of that batch
+
+    Returns {"dir", "files": {name: shape}, "bytes"} for the line."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = arena.device
+    recs = sorted(recs, key=lambda r: r.eventNum)
+    E = len(recs)
+    out = {"records": np.array([[r.eventNum, r.bytes, r.dataId, r.numFragments] for r in recs],
+                               dtype=np.float64).reshape(E, 4)}
+    if E:
+        off = torch.tensor([r.arenaOffset for r in recs], dtype=torch.int64, device=dev)
+        w = torch.arange(B, dtype=torch.int64, device=dev) % 65521 + 1
+        sums = torch.empty((E, 2), dtype=torch.int64, device=dev)
+        for k, r in enumerate(recs):
+            ev = arena[r.arenaOffset: r.arenaOffset + B].to(torch.int64)
+            sums[k, 0] = ev.sum()
+            sums[k, 1] = (ev * w).sum()
+        out["event_sums"] = sums.cpu().numpy().astype(np.float64)
+        P = max(2, min(B, 4096, (4 << 20) // E))
+        pos = np.unique(np.concatenate([[0, B - 1], rng.choice(B, size=max(0, min(B, P) - 2), replace=False)]))
+        idx = off[:, None] + torch.from_numpy(pos).to(dev)[None, :]
+        out["events_sample"] = arena[idx].cpu().numpy().astype(np.float32)
+        out["events_sample_pos"] = pos.astype(np.float64)
+        rows = np.sort(rng.choice(E, size=min(E, 4), replace=False))
+        H = min(B, 1 << 20)
+        out["events_head"] = np.stack([arena[recs[k].arenaOffset: recs[k].arenaOffset + H].cpu().numpy()
+                                       for k in rows]).astype(np.float32)
+        out["events_head_idx"] = rows.astype(np.float64)
+    if n_packets:
+        D = max(1, min(n_packets, (3 << 20) // stride))
+        which = np.sort(rng.choice(n_packets, size=D, replace=False))
+        wd = torch.from_numpy(which).to(dev)
+        slots = packets[: n_packets * stride].view(n_packets, stride)[wd]
+        inside = torch.arange(stride, device=dev)[None, :] < lens[:n_packets][wd][:, None]
+        out["datagrams_sample"] = (slots * inside).cpu().numpy().astype(np.float32)
+        out["datagrams_sample_idx"] = which.astype(np.float64)
+        out["datagram_lengths"] = lens[:n_packets].cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, above the {DUMP_LIMIT}-byte limit")
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {k: list(a.shape) for k, a in out.items()}, "bytes": total}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -363,10 +445,10 @@ def main():
 
     # the other half of north_star's target and BASELINE config 3, in the same run: each a
     # workload of its own (fresh buffers), its own roofline; `value` above stays config 2's
-    subs = sub_legs(args, world)
+    subs = sub_legs(args, world) if args.full else []
     for name in subs:
         over = SUB_LEGS[name]
-        a = argparse.Namespace(**{**vars(args), **over, "cold_steps": 0, "cpu_seconds": 0.0})
+        a = argparse.Namespace(**{**vars(args), **over, "cold_steps": 0, "cpu_seconds": 0.0, "dump_outputs": None})
         t0 = time.perf_counter()
         # At N > 1 a sub-leg runs collectives (the spread leg's RCCL all-to-alls): should one
         # fail or stall, the headline measured above is still reported -- rank 0 prints its
@@ -397,7 +479,7 @@ def main():
                 line[name].update({"parallelism": sl["config"]["parallelism"], "xgmi": sl["xgmi"],
                                    "exchange": sl["spread"]})
 
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if rank == 0:
         _print_line(line)
@@ -459,8 +541,9 @@ SUB_LEGS = {
 
 
 def run_workload(args, env, headline: bool):
-    """One workload: inputs resident in HBM, warmup, a byte-exact round-trip check, the
-    timed steps (max over ranks), per-kernel HIP-event durations and the roofline.
+    """One workload: inputs resident in HBM, warmup, the timed steps (max over ranks) and,
+    with --dump-outputs, the last step's outputs; with --full also a byte-exact round-trip
+    check, per-kernel HIP-event durations, the roofline and the cold receive leg.
     Returns the JSON line (without cpu_baseline)."""
     torch, dist, sar, ctx, dev = env.torch, env.dist, env.sar, env.ctx, env.dev
     world, rank, backend, coll_dev = env.world, env.rank, env.backend, env.coll_dev
@@ -716,8 +799,8 @@ def run_workload(args, env, headline: bool):
     torch.cuda.synchronize()
 
     # ---- correctness gate (outside the timed region): every event byte-exact ----
-    def verify_spread():
-        recs = R.poll()
+    def verify_spread(recs=None):
+        recs = R.poll() if recs is None else recs
         st = R.stats()
         arena = R.arena_tensor()
         owned = sum(1 for r in range(world) for i in range(E) if (r * E + i) % world == rank)
@@ -740,10 +823,11 @@ def run_workload(args, env, headline: bool):
                              f"{owned} owned)")
         return True
 
-    def verify():
+    def verify(recs=None):
+        """recs: the records already polled from R (a poll takes them off its queue)."""
         if spread:
-            return verify_spread()
-        recs = R.poll()
+            return verify_spread(recs)
+        recs = R.poll() if recs is None else recs
         st = R.stats()
         arena = R.arena_tensor()
         ok = (len(recs) == E and st.inProgress == 0 and st.badHeaderDiscards == 0
@@ -759,8 +843,9 @@ def run_workload(args, env, headline: bool):
                              f"eventSuccess={st.eventSuccess} inProgress={st.inProgress})")
         return True
 
+    do_verify = args.full and not args.no_verify
     verified = None
-    if not args.no_verify:
+    if do_verify:
         step()
         torch.cuda.synchronize()
         verified = verify()
@@ -784,7 +869,7 @@ def run_workload(args, env, headline: bool):
     graph = None
     if not args.eager:
         graph = capture(step, G)
-        if not args.no_verify:
+        if do_verify:
             verified = verify() and verified is not False
 
     def run_timed(fn, g, k, gs=None):
@@ -824,8 +909,16 @@ def run_workload(args, env, headline: bool):
     K = args.steps
     elapsed = run_timed(step, graph, K)
     # ...and the events the timed steps left behind, byte for byte (outside the timed region)
-    if not args.no_verify:
-        verified = verify() and verified is not False
+    dump = args.dump_outputs if rank == 0 else None
+    last_recs = R.poll() if (do_verify or dump) else None
+    if do_verify:
+        verified = verify(last_recs) and verified is not False
+    dumped = None
+    if dump:
+        k_last = len(plans) - 1
+        pk, ln = land if spread else bufs[k_last % nbuf]
+        dumped = dump_outputs(dump, torch, R.arena_tensor(), last_recs, B, pk, ln, stride,
+                              plans[k_last].total_packets)
 
     # ---- per-kernel durations: HIP events around each launch of the step, eager, on the
     # stream the kernels run on (the step is single-stream unless --overlap) ----
@@ -849,67 +942,101 @@ def run_workload(args, env, headline: bool):
             per.setdefault(name, []).append(e0.elapsed_time(e1))
         return per
 
-    was_overlap = args.overlap
-    args.overlap = False
-    per = kernel_times(step, args.roofline_steps)
-    args.overlap = was_overlap
-    avg = {k: sum(v) / len(v) for k, v in per.items()}
-    per_launch_events = sum(p.n_events for p in plans) / len(plans)
-    # algorithmic bytes of one launch of each bandwidth kernel:
-    #   seg: B + (B + 36N) per event; reassembly (fused, scatter, scatter+classify): (B + 36N) + B
-    #   (the classify share of scatter+classify -- 24 B of header/length read and 16 B of
-    #   record written per datagram -- is left out, so its rate is understated by ~1 %)
-    launch_bytes = per_launch_events * (2 * B + 36 * npk)
-    bw_kernels = [k for k in avg if k in ("seg_kernel", "reas_kernel", "reas_scatter_kernel",
-                                          "reas_scatter_classify_kernel", "segreas_kernel",
-                                          "reassemble_batch_split", "reassemble_batch_ro")]
-    dom = max(bw_kernels, key=lambda k: sum(per[k]))      # most time in the step
-    dom_ms = avg[dom]
-    if spread and dom == "reas_kernel":
-        # the in-place launches reassemble the events that landed here AND are owned here
-        # (eventNum = rank * E + i): their payload, plus every landed datagram's 36-byte
-        # header read to find out (the foreign payloads are not loaded)
-        here = sum(1 for i in range(E) if (rank * E + i) % world == rank)
-        launch_bytes = (here * (2 * B) + E * 36 * npk) / len(plans)
-    if dom == "segreas_kernel":
-        launch_bytes *= 2                       # both stages' bytes in one launch: 4B + 72N per event
-    achieved = launch_bytes / (dom_ms * 1e-3) / 1e9
+    def roofline_pass():
+        """--full: the per-kernel pass (runs of the step of its own), the copy calibration and
+        the committed PMC traffic; returns the line's `roofline` and `xgmi` entries."""
+        was_overlap = args.overlap
+        args.overlap = False
+        per = kernel_times(step, args.roofline_steps)
+        args.overlap = was_overlap
+        avg = {k: sum(v) / len(v) for k, v in per.items()}
+        per_launch_events = sum(p.n_events for p in plans) / len(plans)
+        # algorithmic bytes of one launch of each bandwidth kernel (SURVEY 8(d)):
+        #   seg: B + (B + 36N) per event; reassembly (fused, scatter, scatter+classify): (B + 36N) + B
+        #   (the classify share of scatter+classify -- 24 B of header/length read and 16 B of
+        #   record written per datagram -- is left out, so its rate is understated by ~1 %)
+        launch_bytes = per_launch_events * (2 * B + 36 * npk)
+        bw_kernels = [k for k in avg if k in ("seg_kernel", "reas_kernel", "reas_scatter_kernel",
+                                              "reas_scatter_classify_kernel", "segreas_kernel",
+                                              "reassemble_batch_split", "reassemble_batch_ro")]
+        dom = max(bw_kernels, key=lambda k: sum(per[k]))      # most time in the step
+        dom_ms = avg[dom]
+        if spread and dom == "reas_kernel":
+            # the in-place launches reassemble the events that landed here AND are owned here
+            # (eventNum = rank * E + i): their payload, plus every landed datagram's 36-byte
+            # header read to find out (the foreign payloads are not loaded)
+            here = sum(1 for i in range(E) if (rank * E + i) % world == rank)
+            launch_bytes = (here * (2 * B) + E * 36 * npk) / len(plans)
+        if dom == "segreas_kernel":
+            launch_bytes *= 2                       # both stages' bytes in one launch: 4B + 72N per event
+        achieved = launch_bytes / (dom_ms * 1e-3) / 1e9
 
-    # HBM traffic per launch of the dominant kernel, from the committed rocprofv3 PMC passes
-    # of this same workload (tools/pmc_summary.py; FETCH_SIZE x2 + WRITE_SIZE, gfx950 rules)
-    traffic, traffic_src = (None, None) if (spread or args.reas != "fused" or args.overlap) else _pmc_traffic(args, dom)
+        # HBM traffic per launch of the dominant kernel, from the committed rocprofv3 PMC passes
+        # of this same workload (tools/pmc_summary.py; FETCH_SIZE x2 + WRITE_SIZE, gfx950 rules)
+        traffic, traffic_src = (None, None) if (spread or args.reas != "fused" or args.overlap) else _pmc_traffic(args, dom)
 
-    # achievable HBM on this device beside the 8 TB/s peak: a plain copy of this
-    # rank's source events (1 GiB) into the arena with e2sar_hip_copy_spans (16-byte
-    # non-temporal loads and stores, one 16-KiB piece per workgroup), HIP events around 5 copies
-    copy_gbps, copy_per = None, None
-    if headline and not spread:
-        copy_gbps, copy_per = copy_calibration(ctx, torch, dev)
+        # achievable HBM on this device beside the 8 TB/s peak (SURVEY 8(d)): a plain copy of this
+        # rank's source events (1 GiB) into the arena with e2sar_hip_copy_spans (16-byte
+        # non-temporal loads and stores, one 16-KiB piece per workgroup), HIP events around 5 copies
+        copy_gbps, copy_per = None, None
+        if headline and not spread:
+            copy_gbps, copy_per = copy_calibration(ctx, torch, dev)
 
-    # spread landing: the exchange's bytes against the xGMI links: this rank's
-    # datagram slots + lengths sent to other ranks per step / the exchange's time
-    xgmi = None
-    if spread and world > 1 and "exchange" in per and sum(per["exchange"]) > 0:
-        # per step: this rank's foreign datagram slots + lengths sent / the exchanges' time
-        # (the step's all-to-alls, each timed on the communication stream; they overlap the
-        # landing of the next batch, so their sum is not a share of the step)
-        sent = pipe.sent * (stride + 4)
-        ex_ms = sum(per["exchange"]) / max(1, args.roofline_steps)
-        xgmi = {"bytes_sent_per_step": sent, "exchange_ms_per_step": round(ex_ms, 5),
-                "exchanges_per_step": len(per["exchange"]) // max(1, args.roofline_steps),
-                "achieved": round(sent / (ex_ms * 1e-3) / 1e9, 1), "peak": XGMI_PEAK_GBS,
-                "unit": "GB/s", "frac": round(sent / (ex_ms * 1e-3) / 1e9 / XGMI_PEAK_GBS, 4),
-                "backend": backend}
+        # spread landing: the exchange's bytes against the xGMI links (SURVEY 8(e)): this rank's
+        # datagram slots + lengths sent to other ranks per step / the exchange's time
+        xgmi = None
+        if spread and world > 1 and "exchange" in per and sum(per["exchange"]) > 0:
+            # per step: this rank's foreign datagram slots + lengths sent / the exchanges' time
+            # (the step's all-to-alls, each timed on the communication stream; they overlap the
+            # landing of the next batch, so their sum is not a share of the step)
+            sent = pipe.sent * (stride + 4)
+            ex_ms = sum(per["exchange"]) / max(1, args.roofline_steps)
+            xgmi = {"bytes_sent_per_step": sent, "exchange_ms_per_step": round(ex_ms, 5),
+                    "exchanges_per_step": len(per["exchange"]) // max(1, args.roofline_steps),
+                    "achieved": round(sent / (ex_ms * 1e-3) / 1e9, 1), "peak": XGMI_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(sent / (ex_ms * 1e-3) / 1e9 / XGMI_PEAK_GBS, 4),
+                    "backend": backend}
+        return {
+            "bound": "hbm",
+            "kernel": dom,
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_unit": "bytes per launch (rocprofv3 PMC, committed)" if traffic else None,
+            "traffic_source": traffic_src,
+            "avg_launch_ms": {k: round(v, 5) for k, v in avg.items()},
+            "launches_per_step": {k: len(v) // max(1, args.roofline_steps) for k, v in per.items()},
+            "algorithmic_bytes_per_launch": int(launch_bytes),
+            "step_achieved_GBps": round(step_bytes * K / elapsed / 1e9, 1),
+            "copy_GBps": round(copy_gbps, 1) if copy_gbps else None,
+            "copy_what": ("best device-to-device copy on this GPU (e2sar_hip_copy_spans, 16-B non-temporal "
+                          "loads/stores, 8-KiB pieces) of 1 and 4 GiB of random bytes, read + write bytes"),
+            "copy_GBps_by_size": copy_per,
+            "frac_of_copy": round(achieved / copy_gbps, 4) if copy_gbps else None,
+            # the best plain copy ever measured on MI355X in this repository (DESIGN 4.3:
+            # tools/ubench_copy.hip, aligned 16-B non-temporal copy of 1 GiB), so the
+            # fraction is never taken against a slower copy than the best one known
+            "best_copy_GBps": BEST_COPY_GBS,
+            "frac_of_best_copy": round(achieved / max(BEST_COPY_GBS, copy_gbps or 0.0), 4),
+        }, xgmi
 
     total_payload = E * B * world * K
     value = total_payload / elapsed / 2**30
     step_bytes = E * (4 * B + 72 * npk)
+    if args.full:
+        roofline, xgmi = roofline_pass()
+    else:
+        # a plain run has the timed steps only: the step's algorithmic bytes against the peak
+        roofline, xgmi = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "step_achieved_GBps": round(step_bytes * K / elapsed / 1e9, 1)}, None
 
     # ---- cold receive-only leg: every batch's datagrams in a buffer of its own, written
     # once before timing; a step reassembles them all (1.1 GB of datagrams > the 256 MiB
     # Infinity Cache, so each launch reads its batch back from HBM) ----
     cold = None
-    if args.cold_steps > 0 and not spread:
+    if args.full and args.cold_steps > 0 and not spread:
         # a reassembler of its own, told its datagrams are cold (streaming loads in the
         # scatter, E2SAR_HIP_REAS_COLD_DATAGRAMS); verify() and the steps below use it
         R_hot = R
@@ -1037,37 +1164,15 @@ def run_workload(args, env, headline: bool):
                 "landing": args.landing,
                 "payload": args.payload,
                 "verified_roundtrip": verified,
-                "verified_at": None if args.no_verify else
+                "verified_at": None if not do_verify else
                 ["an eager step", "the captured graph's first replay", "the timed steps' last step"]
                 if graph is not None else ["an eager step", "the timed steps' last step"],
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom,
-                "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_unit": "bytes per launch (rocprofv3 PMC, committed)" if traffic else None,
-                "traffic_source": traffic_src,
-                "avg_launch_ms": {k: round(v, 5) for k, v in avg.items()},
-                "launches_per_step": {k: len(v) // max(1, args.roofline_steps) for k, v in per.items()},
-                "algorithmic_bytes_per_launch": int(launch_bytes),
-                "step_achieved_GBps": round(step_bytes * K / elapsed / 1e9, 1),
-                "copy_GBps": round(copy_gbps, 1) if copy_gbps else None,
-                "copy_what": ("best device-to-device copy on this GPU (e2sar_hip_copy_spans, 16-B non-temporal "
-                              "loads/stores, 8-KiB pieces) of 1 and 4 GiB of random bytes, read + write bytes"),
-                "copy_GBps_by_size": copy_per,
-                "frac_of_copy": round(achieved / copy_gbps, 4) if copy_gbps else None,
-                # the best plain copy ever measured on MI355X in this repository (DESIGN 4.3:
-                # tools/ubench_copy.hip, aligned 16-B non-temporal copy of 1 GiB), so the
-                # fraction is never taken against a slower copy than the best one known
-                "best_copy_GBps": BEST_COPY_GBS,
-                "frac_of_best_copy": round(achieved / max(BEST_COPY_GBS, copy_gbps or 0.0), 4),
-            },
+            "roofline": roofline,
             "xgmi": xgmi,
             "reas_cold": cold,
+            "full": bool(args.full),
+            "outputs": dumped,
         }
         if spread:
             line["spread"] = {"foreign_sent_per_step": pipe.sent, "received_per_step": pipe.received,

@@ -16,6 +16,55 @@ def test_defaults_are_the_headline_workload(monkeypatch):
     assert a.reas == "fused" and a.landing == "own" and a.payload == "random" and not a.eager
 
 
+def test_a_plain_run_is_lean_by_default():
+    # --full (everything beside the headline figure) and --dump-outputs are off unless asked for
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_what_the_events_hold(tmp_path):
+    # dump_outputs on host tensors: two events lying in the arena out of eventNum order, one
+    # batch of three datagram slots with stale bytes past their lengths
+    import numpy as np
+    import torch
+
+    from e2sar_amd import _capi
+
+    B, stride = 5000, 64
+    rng = np.random.default_rng(7)
+    ev = rng.integers(0, 256, (2, B), dtype=np.uint8)
+    arena = torch.zeros(3 * 8192, dtype=torch.uint8)
+    arena[8192: 8192 + B] = torch.from_numpy(ev[0])
+    arena[0: B] = torch.from_numpy(ev[1])
+    recs = [_capi.EventRec(eventNum=11, arenaOffset=0, bytes=B, dataId=4321, numFragments=4),
+            _capi.EventRec(eventNum=10, arenaOffset=8192, bytes=B, dataId=4321, numFragments=4)]
+    slots = rng.integers(1, 256, (3, stride), dtype=np.uint8)
+    lens = np.array([64, 10, 33], dtype=np.int32)
+    res = bench.dump_outputs(str(tmp_path / "o"), torch, arena, recs, B, torch.from_numpy(slots.reshape(-1)),
+                             torch.from_numpy(lens), stride, 3)
+    got = {n: np.load(tmp_path / "o" / (n + ".npy")) for n in res["files"]}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert res["bytes"] == sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT
+    assert got["records"].tolist() == [[10, B, 4321, 4], [11, B, 4321, 4]]
+    w = np.arange(B, dtype=np.int64) % 65521 + 1
+    assert got["event_sums"].tolist() == [[int(e.sum()), int((e.astype(np.int64) * w).sum())] for e in ev]
+    pos = got["events_sample_pos"].astype(np.int64)
+    assert pos[0] == 0 and pos[-1] == B - 1 and len(set(pos.tolist())) == len(pos)
+    assert np.array_equal(got["events_sample"], ev[:, pos].astype(np.float32))
+    assert np.array_equal(got["events_head"], ev[got["events_head_idx"].astype(np.int64)].astype(np.float32))
+    assert got["datagram_lengths"].tolist() == [64, 10, 33]
+    which = got["datagrams_sample_idx"].astype(np.int64)
+    want = slots[which] * (np.arange(stride)[None, :] < lens[which][:, None])
+    assert which.tolist() == [0, 1, 2] and np.array_equal(got["datagrams_sample"], want.astype(np.float32))
+    # the same arguments give the same files
+    res2 = bench.dump_outputs(str(tmp_path / "p"), torch, arena, recs, B, torch.from_numpy(slots.reshape(-1)),
+                              torch.from_numpy(lens), stride, 3)
+    assert res2["files"] == res["files"]
+    assert all(np.array_equal(got[n], np.load(tmp_path / "p" / (n + ".npy"))) for n in got)
+
+
 def test_cpu_baseline_reports_the_contract_fields(monkeypatch):
     monkeypatch.setenv("OMP_NUM_THREADS", "2")
     args = argparse.Namespace(event_bytes=65536, mtu=1500, lb_version=2)

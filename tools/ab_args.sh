@@ -10,7 +10,7 @@ for spec in "$@"; do
   i=$((i + 1))
   name=${spec%%|*}; args=${spec#*|}
   [ "$args" = "$spec" ] && args=""
-  timeout -k 10 200 python bench.py --cpu-seconds 0 $args > $O/${i}_$name.json 2> $O/${i}_$name.err || { tail -20 $O/${i}_$name.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --cpu-seconds 0 $args > $O/${i}_$name.json 2> $O/${i}_$name.err || { tail -20 $O/${i}_$name.err; exit 1; }
   python - $O/${i}_$name.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,16 +1,18 @@
 #!/bin/bash
 # Run bench.py once per environment setting.  Usage: tools/ab_env.sh TAG "bench args" "NAME:VAR=V,VAR=V" ...
-# (a setting with no VAR after the colon runs the default build and environment)
+# (a setting with no VAR after the colon runs the default build and environment;
+# results under ${E2SAR_OUT:-bench_out}/TAG)
 set -e
 TAG=$1; ARGS=$2; shift 2
-mkdir -p gpurun_out/$TAG
+O=${E2SAR_OUT:-bench_out}/$TAG
+mkdir -p $O
 for spec in "$@"; do
   name=${spec%%:*}; vars=${spec#*:}
-  env $(echo "$vars" | tr ',' ' ') timeout -k 10 200 python bench.py --cpu-seconds 0 $ARGS > gpurun_out/$TAG/$name.json 2> gpurun_out/$TAG/$name.err
+  env $(echo "$vars" | tr ',' ' ') timeout -k 10 200 python bench.py --full --cpu-seconds 0 $ARGS > $O/$name.json 2> $O/$name.err
 done
 for spec in "$@"; do
   name=${spec%%:*}
-  python - gpurun_out/$TAG/$name.json <<'PY'
+  python - $O/$name.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 c = d.get("reas_cold") or {}

@@ -9,7 +9,7 @@ mkdir -p $O
 for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     if [ "$v" = base ]; then L=$(pwd)/e2sar_amd/lib/libe2sar_hip.so; else L=$ROOTDIR/build/variants/lib_$v.so; fi
-    E2SAR_HIP_LIB=$L timeout -k 10 200 python bench.py --cpu-seconds 0 --cold-steps 0 --subs none $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "$v failed"; tail -5 $O/${v}_$rep.err; exit 1; }
+    E2SAR_HIP_LIB=$L timeout -k 10 200 python bench.py --full --cpu-seconds 0 --cold-steps 0 --subs none $ARGS > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "$v failed"; tail -5 $O/${v}_$rep.err; exit 1; }
     python3 - $O/${v}_$rep.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

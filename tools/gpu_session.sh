@@ -8,7 +8,8 @@
 #     ab=REPS:ARGS:NAMES    interleaved bench A/B of library builds (tools/ab_libs.sh);
 #                           NAMES comma-separated, "base" = the tree's library
 #     prof=WORKLOADS        rocprofv3 stats + PMC per workload (tools/profile_round4.sh)
-#     bench=ARGS            one bench.py run, its JSON line to bench_N.json
+#     bench=ARGS            one bench.py run, its JSON line to bench_N.json (ARGS with --full for
+#                           the roofline, cold leg, sub-legs and CPU baseline beside the headline)
 #     smoke                 __graft_entry__.smoke()
 #     cmd=SHELL             any other command (its own 300 s limit)
 set -o pipefail

@@ -20,11 +20,11 @@ for w in $W; do
   if [ $w = pre ]; then export E2SAR_HIP_LIB=$R/build/variants/lib_pre.so; else unset E2SAR_HIP_LIB; fi
   mkdir -p $O/$w
   echo "== $w stats" >> $O/progress.log
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$w/stats -o run -- python3 $R/bench.py --cpu-seconds 0 --steps 8 --warmup 1 --cold-steps 4 $A > $O/$w/bench_profiled.json 2> $O/$w/stats.log
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$w/stats -o run -- python3 $R/bench.py --full --cpu-seconds 0 --steps 8 --warmup 1 --cold-steps 4 $A > $O/$w/bench_profiled.json 2> $O/$w/stats.log
   if [ -n "$WL" ]; then
     echo "== $w pmc" >> $O/progress.log
-    timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/$w/fetch -o run -- python3 $R/bench.py --cpu-seconds 0 --steps 2 --warmup 1 --cold-steps 2 --no-verify --eager $A > $O/$w/fetch.log 2>&1
-    timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/$w/write -o run -- python3 $R/bench.py --cpu-seconds 0 --steps 2 --warmup 1 --cold-steps 2 --no-verify --eager $A > $O/$w/write.log 2>&1
+    timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/$w/fetch -o run -- python3 $R/bench.py --full --cpu-seconds 0 --steps 2 --warmup 1 --cold-steps 2 --no-verify --eager $A > $O/$w/fetch.log 2>&1
+    timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/$w/write -o run -- python3 $R/bench.py --full --cpu-seconds 0 --steps 2 --warmup 1 --cold-steps 2 --no-verify --eager $A > $O/$w/write.log 2>&1
     python3 $R/tools/pmc_summary.py $O/$w/fetch $O/$w/write $O/$w/pmc_summary.json --workload $WL > /dev/null
   fi
 done
