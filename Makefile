@@ -6,7 +6,7 @@ INC := -Iinclude -Ie2sar_amd/csrc
 LIBDIR := e2sar_amd/lib
 
 HIP_SRCS := e2sar_amd/csrc/sar_kernels.hip e2sar_amd/csrc/capi.cpp
-HIP_HDRS := include/e2sar_hip.h e2sar_amd/csrc/sar_kernels.hpp e2sar_amd/csrc/wire.hpp
+HIP_HDRS := include/e2sar_hip.h $(wildcard e2sar_amd/csrc/*.hpp)
 
 all: $(LIBDIR)/libe2sar_hip.so oracle
 

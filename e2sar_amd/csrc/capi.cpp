@@ -2,8 +2,8 @@
 //
 // Host-side glue only: argument checks (mirroring the reference's sanity checks),
 // device allocation of the reassembly state, and the hand-off of device records to
-// the caller.  Every byte of event or datagram data is moved by the kernels in
-// sar_kernels.hip; there is no CPU fallback.
+// the caller.  Every byte of event or datagram data is moved by the kernels of
+// sar_kernels.hip (its device headers); there is no CPU fallback.
 #ifndef E2SAR_HIP_EXPERIMENTAL
 #define E2SAR_HIP_EXPERIMENTAL 0
 #endif
@@ -21,6 +21,7 @@
 #include <set>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "e2sar_hip.h"
@@ -115,6 +116,66 @@ static hipError_t note_launch(e2sar_hip_reas *r, hipStream_t s)
     if (capturing(s)) r->sawCapture = true;          // replays run wherever the caller puts them
     else r->streams.insert(s);
     return hipSuccess;
+}
+
+// The prologue and epilogue of every launch through a reassembler: r must not be NULL; under
+// r->mu, on the device and (stream == NULL) the default stream of r's context -- or of `on`,
+// where the caller names another context -- run body(s), then remember the stream
+// (note_launch).  body returns the launch's hipError_t, reported as "<what>: <error>", or,
+// where it can fail in other ways or words, an ABI code with the message already set.
+template <typename Body>
+static int reas_launch(e2sar_hip_reas *r, void *stream, const char *what, Body body, const e2sar_hip_ctx *on = nullptr)
+{
+    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (!on) on = r->ctx;
+    HIP_TRY(hipSetDevice(on->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : on->stream;
+    hipError_t e = hipSuccess;
+    if constexpr (std::is_same_v<decltype(body(s)), hipError_t>) e = body(s);
+    else if (int rc = body(s)) return rc;
+    if (e == hipSuccess) e = note_launch(r, s);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return E2SAR_HIP_OK;
+}
+
+/* ---------------- argument checks shared by the entry points ---------------- */
+
+// A batch of nPackets datagram slots of `stride` bytes at d_packets, for reassembler r.
+static int check_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
+{
+    const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
+    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
+    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
+    return E2SAR_HIP_OK;
+}
+
+// The caller's work buffer of a classified batch of n datagrams; tooSmall is the entry
+// point's own wording of that failure.
+static int check_work(const void *d_work, size_t workBytes, uint32_t n, const char *tooSmall)
+{
+    if (((uintptr_t)d_work & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
+    if (workBytes < work_bytes(n)) return fail(E2SAR_HIP_ERR_PARAMETER, tooSmall);
+    return E2SAR_HIP_OK;
+}
+
+// The datagram layout a segmentation writes: maxPldLen (udpBound: at most a UDP datagram's),
+// the slot stride, the packet buffer's alignment (a NULL buffer passes: its caller checks).
+static int check_seg_layout(uint32_t maxPldLen, uint32_t stride, const uint8_t *d_packets, bool udpBound = true)
+{
+    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
+    if (udpBound && maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen above a UDP datagram");
+    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
+        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
+    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    return E2SAR_HIP_OK;
+}
+
+static int check_world(uint32_t world, uint32_t self)
+{
+    if (world == 0 || world > 64 || self >= world) return fail(E2SAR_HIP_ERR_PARAMETER, "world must be 1..64, self < world");
+    return E2SAR_HIP_OK;
 }
 
 // reassemble_batch keeps the fused kernel up to this many bytes of datagram slots (a batch
@@ -460,11 +521,7 @@ int e2sar_hip_segment_batch(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_eve
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
     if (nEvents == 0) return E2SAR_HIP_OK;
     if (!d_events || !d_packets) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
-    if (maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen above a UDP datagram");
-    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
-        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
     (void)eventsDwordAligned;        // a hint only: the kernel checks every event's address itself
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
@@ -481,11 +538,7 @@ int e2sar_hip_segment_batch_dev(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
     if (maxEvents == 0) return E2SAR_HIP_OK;
     if (!d_events || !d_counts || !d_packets) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
-    if (maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen above a UDP datagram");
-    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
-        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     hipError_t e = launch_segment(d_events, maxEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen,
@@ -632,43 +685,36 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (nPackets == 0) return E2SAR_HIP_OK;
     if (!d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
-    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
-    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    auto &sc = r->scratch[s];
-    if (ref_order(r)) {
-        // classify in arrival order into the internal work buffer, then the scatter kernel
-        if (int rc = ro_prepare(r, s, nPackets)) return rc;
-        if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
-        hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork);
-        if (e == hipSuccess)
-            e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, cold_loads(r, nPackets, stride));
-        if (e == hipSuccess) e = note_launch(r, s);
-        if (e != hipSuccess) return hip_fail(e, "reference-order reassembly launch");
+    if (int st = check_batch(r, d_packets, stride, nPackets)) return st;
+    return reas_launch(r, stream, "reassembly launch", [&](hipStream_t s) -> int {
+        auto &sc = r->scratch[s];
+        if (ref_order(r)) {
+            // classify in arrival order into the internal work buffer, then the scatter kernel
+            if (int rc = ro_prepare(r, s, nPackets)) return rc;
+            if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
+            hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork);
+            if (e == hipSuccess)
+                e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, cold_loads(r, nPackets, stride));
+            if (e != hipSuccess) return hip_fail(e, "reference-order reassembly launch");
+            return E2SAR_HIP_OK;
+        }
+        // A batch whose datagrams cannot still be in the 256 MiB Infinity Cache (more than
+        // kFusedMaxBytes of slots) is read back from HBM whatever the caller did before, and
+        // there the split form -- classify, then one-round scatter workgroups with streaming
+        // loads -- is the faster one: 8 MiB events at MTU 9000, 70 per launch (65,730
+        // datagrams, BASELINE config 3): 1116 GiB/s fused vs 1302 split.  Internal work buffer
+        // of this stream, grown on first use (outside graph capture).
+        if ((uint64_t)nPackets * stride > kFusedMaxBytes) {
+            if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
+            hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork, s);
+            if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, true);
+            if (e != hipSuccess) return hip_fail(e, "reassembly launch (split form)");
+            return E2SAR_HIP_OK;
+        }
+        const hipError_t e = launch_reassemble(r->dev, d_packets, stride, d_lens, nPackets, now_ms, s);
+        if (e != hipSuccess) return hip_fail(e, "reassembly launch");
         return E2SAR_HIP_OK;
-    }
-    // A batch whose datagrams cannot still be in the 256 MiB Infinity Cache (more than
-    // kFusedMaxBytes of slots) is read back from HBM whatever the caller did before, and
-    // there the split form -- classify, then one-round scatter workgroups with streaming
-    // loads -- is the faster one: 8 MiB events at MTU 9000, 70 per launch (65,730
-    // datagrams, BASELINE config 3): 1116 GiB/s fused vs 1302 split.  Internal work buffer
-    // of this stream, grown on first use (outside graph capture).
-    if ((uint64_t)nPackets * stride > kFusedMaxBytes) {
-        if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
-        hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork, s);
-        if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, true);
-        if (e == hipSuccess) e = note_launch(r, s);
-        if (e != hipSuccess) return hip_fail(e, "reassembly launch (split form)");
-        return E2SAR_HIP_OK;
-    }
-    hipError_t e = launch_reassemble(r->dev, d_packets, stride, d_lens, nPackets, now_ms, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "reassembly launch");
-    return E2SAR_HIP_OK;
+    });
 }
 
 #if E2SAR_HIP_EXPERIMENTAL
@@ -678,9 +724,8 @@ int e2sar_hip_seg_groups(const e2sar_hip_seg_event *events, uint32_t nEvents, ui
     if (!nGroups) return fail(E2SAR_HIP_ERR_PARAMETER, "nGroups is NULL");
     *nGroups = 0;
     if (nEvents && (!events || !starts)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL table");
-    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
-    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
-        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
+    // a host-side plan: no packet buffer, and maxPldLen has never been bounded here
+    if (int rc = check_seg_layout(maxPldLen, stride, nullptr, false)) return rc;
     *nGroups = seg_groups(events, nEvents, maxPacketsPerEvent, maxPldLen, stride, starts, cap);
     return E2SAR_HIP_OK;
 }
@@ -694,18 +739,11 @@ int e2sar_hip_reassemble_groups(e2sar_hip_reas *r, const uint8_t *d_packets, uin
     if (nGroups == 0 || !d_starts || ref_order(r) || (uint64_t)nPackets * stride > kFusedMaxBytes)
         return e2sar_hip_reassemble_batch(r, d_packets, stride, d_lens, nPackets, now_ms, stream);
     if (!d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
-    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
-    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
+    if (int st = check_batch(r, d_packets, stride, nPackets)) return st;
     if (nGroups > 0x7FFFFFFFu) return fail(E2SAR_HIP_ERR_PARAMETER, "too many groups");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e = launch_reassemble_groups(r->dev, d_packets, stride, d_lens, nPackets, d_starts, nGroups, now_ms, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "reassembly launch (groups)");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "reassembly launch (groups)", [&](hipStream_t s) {
+        return launch_reassemble_groups(r->dev, d_packets, stride, d_lens, nPackets, d_starts, nGroups, now_ms, s);
+    });
 }
 
 static int segreas(e2sar_hip_ctx *ctx, const e2sar_hip_segreas_batch *batches, uint32_t nBatches, int lbHdrVersion,
@@ -713,10 +751,7 @@ static int segreas(e2sar_hip_ctx *ctx, const e2sar_hip_segreas_batch *batches, u
 {
     if (!ctx || !r || (!batches && nBatches)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
     if (nBatches > kChainMaxBatches) return fail(E2SAR_HIP_ERR_PARAMETER, "more than 8 batches per launch");
-    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
-    if (maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen above a UDP datagram");
-    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
-        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
+    if (int rc = check_seg_layout(maxPldLen, stride, nullptr)) return rc;      // packet buffers: per batch, below
     if (!r->cfg.withLBHeader) return fail(E2SAR_HIP_ERR_PARAMETER, "the chained form emits LB headers: withLBHeader required");
     if (ref_order(r)) return fail(E2SAR_HIP_ERR_PARAMETER, "the chained form is order-insensitive (no REFERENCE_ORDER)");
     ChainBatches cb{};
@@ -741,21 +776,19 @@ static int segreas(e2sar_hip_ctx *ctx, const e2sar_hip_segreas_batch *batches, u
         words += x.nPackets;
     }
     if (cb.nb == 0) return E2SAR_HIP_OK;
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    auto &sc = r->scratch[s];
-    if (int rc = grow(r, s, sc.tiles, sc.tilesBytes, 4ull * words)) return rc;
-    for (uint32_t b = 0; b < cb.nb; b++)
-        cb.b[b].tiles = static_cast<uint32_t *>(sc.tiles) + reinterpret_cast<uintptr_t>(cb.b[b].tiles);
-    // the launch's ready counters start at 0: zeroed by a kernel (capture-safe)
-    // before every launch, so a group that gave up waiting in an earlier launch (error bit 4)
-    // cannot leave a count behind for this one
-    hipError_t e = launch_zero_words(sc.tiles, words, s);
-    if (e == hipSuccess) e = launch_segreas(cb, lbHdrVersion, maxPldLen, stride, r->dev, now_ms, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "segreas_kernel launch");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "segreas_kernel launch", [&](hipStream_t s) -> int {
+        auto &sc = r->scratch[s];
+        if (int rc = grow(r, s, sc.tiles, sc.tilesBytes, 4ull * words)) return rc;
+        for (uint32_t b = 0; b < cb.nb; b++)
+            cb.b[b].tiles = static_cast<uint32_t *>(sc.tiles) + reinterpret_cast<uintptr_t>(cb.b[b].tiles);
+        // the launch's ready counters start at 0: zeroed by a kernel (capture-safe)
+        // before every launch, so a group that gave up waiting in an earlier launch (error bit 4)
+        // cannot leave a count behind for this one
+        hipError_t e = launch_zero_words(sc.tiles, words, s);
+        if (e == hipSuccess) e = launch_segreas(cb, lbHdrVersion, maxPldLen, stride, r->dev, now_ms, s);
+        if (e != hipSuccess) return hip_fail(e, "segreas_kernel launch");
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_segment_reassemble_batch(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_events, uint32_t nEvents,
@@ -783,23 +816,10 @@ int e2sar_hip_relay_plan(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t maxEv
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (!d_events || !d_counts) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
     if (maxPldLen == 0 || maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "bad maxPldLen");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e = launch_relay_plan(r->dev, firstRecord, maxEvents, (uint32_t)maxPldLen, lbTick, entropyBase,
-                                     d_events, d_counts, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "relay_plan launch");
-    return E2SAR_HIP_OK;
-}
-
-static int check_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
-{
-    const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
-    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
-    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "relay_plan launch", [&](hipStream_t s) {
+        return launch_relay_plan(r->dev, firstRecord, maxEvents, (uint32_t)maxPldLen, lbTick, entropyBase, d_events,
+                                 d_counts, s);
+    });
 }
 
 size_t e2sar_hip_reas_work_bytes(uint32_t nPackets) { return work_bytes(nPackets); }
@@ -811,22 +831,19 @@ int e2sar_hip_reas_classify(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (nPackets == 0) return E2SAR_HIP_OK;
     if (!d_packets || !d_lens || !d_work) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (((uintptr_t)d_work & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
-    if (workBytes < work_bytes(nPackets)) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer too small");
+    if (int st = check_work(d_work, workBytes, nPackets, "work buffer too small")) return st;
     if (int st = check_batch(r, d_packets, stride, nPackets)) return st;
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e;
-    if (ref_order(r)) {
-        if (int rc = ro_prepare(r, s, nPackets)) return rc;
-        e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, d_work);
-    } else {
-        e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, d_work, s);
-    }
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "classify launch");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "classify launch", [&](hipStream_t s) -> int {
+        hipError_t e;
+        if (ref_order(r)) {
+            if (int rc = ro_prepare(r, s, nPackets)) return rc;
+            e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, d_work);
+        } else {
+            e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, d_work, s);
+        }
+        if (e != hipSuccess) return hip_fail(e, "classify launch");
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_reas_scatter(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets,
@@ -835,16 +852,11 @@ int e2sar_hip_reas_scatter(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (nPackets == 0) return E2SAR_HIP_OK;
     if (!d_packets || !d_work) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (((uintptr_t)d_work & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
-    if (workBytes < work_bytes(nPackets)) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer too small");
+    if (int st = check_work(d_work, workBytes, nPackets, "work buffer too small")) return st;
     if (int st = check_batch(r, d_packets, stride, nPackets)) return st;
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, d_work, s, cold_loads(r, nPackets, stride));
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "scatter launch");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "scatter launch", [&](hipStream_t s) {
+        return launch_reas_scatter(r->dev, d_packets, stride, nPackets, d_work, s, cold_loads(r, nPackets, stride));
+    });
 }
 
 int e2sar_hip_reas_scatter_classify(e2sar_hip_reas *r, uint32_t stride, const uint8_t *d_spk, uint32_t sn,
@@ -856,50 +868,39 @@ int e2sar_hip_reas_scatter_classify(e2sar_hip_reas *r, uint32_t stride, const ui
     if (sn == 0 && cn == 0) return E2SAR_HIP_OK;
     if (sn) {
         if (!d_spk || !d_swork) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer (scatter batch)");
-        if (((uintptr_t)d_swork & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
-        if (sworkBytes < work_bytes(sn)) return fail(E2SAR_HIP_ERR_PARAMETER, "scatter work buffer too small");
+        if (int st = check_work(d_swork, sworkBytes, sn, "scatter work buffer too small")) return st;
         if (int st = check_batch(r, d_spk, stride, sn)) return st;
     }
     if (cn) {
         if (!d_cpk || !d_clens || !d_cwork) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer (classify batch)");
-        if (((uintptr_t)d_cwork & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
-        if (cworkBytes < work_bytes(cn)) return fail(E2SAR_HIP_ERR_PARAMETER, "classify work buffer too small");
+        if (int st = check_work(d_cwork, cworkBytes, cn, "classify work buffer too small")) return st;
         if (int st = check_batch(r, d_cpk, stride, cn)) return st;
     }
     if (sn && cn && d_swork == d_cwork) return fail(E2SAR_HIP_ERR_PARAMETER, "the two batches need different work buffers");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e;
-    if (ref_order(r)) {
-        // arrival order needs the classification of b+1 after that of b, not inside the
-        // scatter of b: two launches, same results.  (Round 5: the classification of b+1 on
-        // a side stream beside the scatter of b measured slower -- the scatter 63 -> 102-113
-        // us beside it, DESIGN.md 3 -- so the two run in line.)
-        e = launch_reas_scatter(r->dev, d_spk, stride, sn, d_swork, s, cold_loads(r, sn, stride));
-        if (e == hipSuccess && cn) {
-            if (int rc = ro_prepare(r, s, cn)) return rc;
-            e = ro_classify(r, s, d_cpk, stride, d_clens, cn, now_ms, d_cwork);
+    return reas_launch(r, stream, "scatter_classify launch", [&](hipStream_t s) -> int {
+        hipError_t e;
+        if (ref_order(r)) {
+            // arrival order needs the classification of b+1 after that of b, not inside the
+            // scatter of b: two launches, same results.  (Round 5: the classification of b+1 on
+            // a side stream beside the scatter of b measured slower -- the scatter 63 -> 102-113
+            // us beside it, DESIGN.md 3 -- so the two run in line.)
+            e = launch_reas_scatter(r->dev, d_spk, stride, sn, d_swork, s, cold_loads(r, sn, stride));
+            if (e == hipSuccess && cn) {
+                if (int rc = ro_prepare(r, s, cn)) return rc;
+                e = ro_classify(r, s, d_cpk, stride, d_clens, cn, now_ms, d_cwork);
+            }
+        } else {
+            e = launch_reas_scatter_classify(r->dev, stride, d_spk, sn, d_swork, d_cpk, d_clens, cn, now_ms, d_cwork, s,
+                                             cold_loads(r, sn, stride));
         }
-    } else {
-        e = launch_reas_scatter_classify(r->dev, stride, d_spk, sn, d_swork, d_cpk, d_clens, cn, now_ms, d_cwork, s,
-                                         cold_loads(r, sn, stride));
-    }
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "scatter_classify launch");
-    return E2SAR_HIP_OK;
+        if (e != hipSuccess) return hip_fail(e, "scatter_classify launch");
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_reas_gc(e2sar_hip_reas *r, uint64_t now_ms, uint64_t timeout_ms, void *stream)
 {
-    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    hipError_t e = launch_gc(r->dev, now_ms, timeout_ms, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "gc launch");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "gc launch", [&](hipStream_t s) { return launch_gc(r->dev, now_ms, timeout_ms, s); });
 }
 
 // Wait until every kernel launched through this reassembler has finished (caller holds
@@ -1072,15 +1073,12 @@ static int recycle_check(e2sar_hip_reas *r, int force, hipStream_t s)
 
 int e2sar_hip_reas_recycle(e2sar_hip_reas *r, int force, void *stream)
 {
-    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    if (int rc = recycle_check(r, force, s)) return rc;
-    hipError_t e = launch_recycle(r->dev, force != 0, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "recycle launch");
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "recycle launch", [&](hipStream_t s) -> int {
+        if (int rc = recycle_check(r, force, s)) return rc;
+        const hipError_t e = launch_recycle(r->dev, force != 0, s);
+        if (e != hipSuccess) return hip_fail(e, "recycle launch");
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_segment_batch_recycle(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_events, uint32_t nEvents,
@@ -1092,61 +1090,52 @@ int e2sar_hip_segment_batch_recycle(e2sar_hip_ctx *ctx, const e2sar_hip_seg_even
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (r->ctx->device != ctx->device) return fail(E2SAR_HIP_ERR_PARAMETER, "reassembler on another device");
     if (nEvents && (!d_events || !d_packets)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (maxPldLen == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen is 0 (MTU too small)");
-    if (maxPldLen > 65535u) return fail(E2SAR_HIP_ERR_PARAMETER, "maxPldLen above a UDP datagram");
-    if ((stride & 15u) || stride < E2SAR_HIP_LBRE_HDR_LEN + maxPldLen)
-        return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and hold 36 + maxPldLen");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
     (void)eventsDwordAligned;
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    if (int rc = recycle_check(r, force, s)) return rc;
-    hipError_t e = launch_segment(d_events, nEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen, d_packets, stride,
-                                  d_lens, s, nullptr, &r->dev, force != 0);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "seg_kernel + recycle launch");
-    return E2SAR_HIP_OK;
+    // unlike its siblings, on the segmenter context's device and default stream, not r's
+    return reas_launch(r, stream, "seg_kernel + recycle launch", [&](hipStream_t s) -> int {
+        if (int rc = recycle_check(r, force, s)) return rc;
+        const hipError_t e = launch_segment(d_events, nEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen, d_packets,
+                                            stride, d_lens, s, nullptr, &r->dev, force != 0);
+        if (e != hipSuccess) return hip_fail(e, "seg_kernel + recycle launch");
+        return E2SAR_HIP_OK;
+    }, ctx);
 }
 
 int e2sar_hip_reas_compact(e2sar_hip_reas *r, void *stream)
 {
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
-    std::lock_guard<std::mutex> lk(r->mu);
+    // (set at creation: whether the alternate table exists never changes, so no lock to ask)
     if (!r->alt.slots) return fail(E2SAR_HIP_ERR_LOGIC, "reassembler was not created COMPACTABLE");
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    ReasCtl c;
-    if (int rc = wait_launches(r)) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&c, r->dev.ctl, sizeof(ReasCtl), hipMemcpyDeviceToHost));
-    if (c.nCompleted != 0) return fail(E2SAR_HIP_ERR_LOGIC, "completed events not yet polled");
-    hipError_t e = launch_compact(r->dev, r->alt, s);
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, "compact launch");
-    std::swap(r->dev.slots, r->alt.slots);
-    std::swap(r->dev.arena, r->alt.arena);
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "compact launch", [&](hipStream_t s) -> int {
+        ReasCtl c;
+        if (int rc = wait_launches(r)) return rc;
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(&c, r->dev.ctl, sizeof(ReasCtl), hipMemcpyDeviceToHost));
+        if (c.nCompleted != 0) return fail(E2SAR_HIP_ERR_LOGIC, "completed events not yet polled");
+        const hipError_t e = launch_compact(r->dev, r->alt, s);
+        if (e != hipSuccess) return hip_fail(e, "compact launch");
+        std::swap(r->dev.slots, r->alt.slots);
+        std::swap(r->dev.arena, r->alt.arena);
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_reas_reset_stats(e2sar_hip_reas *r, void *stream)
 {
-    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
-    std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : r->ctx->stream;
-    // the event counters (eventSuccess .. reassemblyLoss), the per-packet shards and the
-    // error flags; the completed / lost records not yet polled stay queued (resetting
-    // statistics in the reference discards no queued event), and so does inProgress, which
-    // counts live table entries, not history
-    auto *ctl = reinterpret_cast<uint8_t *>(r->dev.ctl);
-    // kernels, not memset nodes: this call may be captured into a HIP graph
-    HIP_TRY(launch_zero_words(ctl + offsetof(ReasCtl, eventSuccess),
-                              (offsetof(ReasCtl, inProgress) - offsetof(ReasCtl, eventSuccess)) / 4, s));
-    HIP_TRY(launch_zero_words(r->dev.shards, sizeof(ReasShard) * kShards / 4, s));
-    HIP_TRY(launch_zero_words(ctl + offsetof(ReasCtl, errorFlags), 1, s));
-    HIP_TRY(note_launch(r, s));
-    return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "reset_stats launch", [&](hipStream_t s) -> int {
+        // the event counters (eventSuccess .. reassemblyLoss), the per-packet shards and the
+        // error flags; the completed / lost records not yet polled stay queued (resetting
+        // statistics in the reference discards no queued event), and so does inProgress, which
+        // counts live table entries, not history
+        auto *ctl = reinterpret_cast<uint8_t *>(r->dev.ctl);
+        // kernels, not memset nodes: this call may be captured into a HIP graph
+        HIP_TRY(launch_zero_words(ctl + offsetof(ReasCtl, eventSuccess),
+                                  (offsetof(ReasCtl, inProgress) - offsetof(ReasCtl, eventSuccess)) / 4, s));
+        HIP_TRY(launch_zero_words(r->dev.shards, sizeof(ReasShard) * kShards / 4, s));
+        HIP_TRY(launch_zero_words(ctl + offsetof(ReasCtl, errorFlags), 1, s));
+        return E2SAR_HIP_OK;
+    });
 }
 
 size_t e2sar_hip_route_workspace_bytes(uint32_t nPackets, uint32_t world)
@@ -1162,7 +1151,7 @@ static int route(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_t stride, 
                  size_t workspaceBytes, void *stream)
 {
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (world == 0 || world > 64 || self >= world) return fail(E2SAR_HIP_ERR_PARAMETER, "world must be 1..64, self < world");
+    if (int rc = check_world(world, self)) return rc;
     if ((stride & 15u) || stride < 48u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16, >= 48");
     if (nPackets && (!d_packets || !d_lens || !d_sendPackets || !d_sendLens || !d_counts || !d_workspace))
         return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
@@ -1201,7 +1190,7 @@ int e2sar_hip_route_append(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_
                            void *d_workspace, size_t workspaceBytes, void *stream)
 {
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (world == 0 || world > 64 || self >= world) return fail(E2SAR_HIP_ERR_PARAMETER, "world must be 1..64, self < world");
+    if (int rc = check_world(world, self)) return rc;
     if ((stride & 15u) || stride < 48u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16, >= 48");
     if (capPerRank == 0 || (uint64_t)capPerRank * world > 0xFFFFFFFFull)
         return fail(E2SAR_HIP_ERR_PARAMETER, "capPerRank must be > 0 and capPerRank * world < 2^32");
@@ -1221,7 +1210,7 @@ int e2sar_hip_route_append(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_
 int e2sar_hip_reas_set_owner(e2sar_hip_reas *r, uint32_t world, uint32_t self)
 {
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
-    if (world == 0 || world > 64 || self >= world) return fail(E2SAR_HIP_ERR_PARAMETER, "world must be 1..64, self < world");
+    if (int rc = check_world(world, self)) return rc;
     std::lock_guard<std::mutex> lk(r->mu);
     r->dev.ownWorld = r->alt.ownWorld = world;
     r->dev.ownSelf = r->alt.ownSelf = self;

@@ -7,7 +7,7 @@ brought (streaming loads, ``set_cold(True)``) on the receive stream -- with frag
 the same events, offset-0 fragments included, on both sides.  The reference never shares an
 in-progress event between receivers (each receive thread owns its map,
 e2sarDPReassembler.hpp:223-229); this build does, through the device table's claim/publish
-protocol (sar_kernels.hip ``find_or_create``) and per-run atomic accumulators.  The first
+protocol (reas_table.hpp ``find_or_create``) and per-run atomic accumulators.  The first
 test runs exactly that split with both launches in flight together (checked with HIP event
 timestamps) and compares events, bytes and every counter with the oracle's reassembly of
 the same datagrams in stream order.

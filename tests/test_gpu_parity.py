@@ -689,7 +689,7 @@ def _singleton_at(order_len, batches, group, pos):
 def test_reas_large_events_with_loss_fused(hip, mtu, batches, group):
     # events of 4-8 MiB through the fused reas_kernel, where run tails of events of at
     # least 4 MiB add to the accumulator after the copy (E2SAR_REAS_DEFER_ACC,
-    # sar_kernels.hip reas_range): A loses one datagram to a bad RE version (never
+    # reas_fused.hpp reas_range): A loses one datagram to a bad RE version (never
     # completes, GC reports it lost), B receives one full datagram twice, in its middle
     # (curBytes passes its length without meeting it, so it never completes -- the
     # reference's rule, cpp:398-403), C arrives with its tail shuffled, D intact.  Events,

@@ -14,6 +14,17 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 SOURCES = ["e2sar_amd/csrc/sar_kernels.hip"]
+# The kernels of the one translation unit (its device code sits in e2sar_amd/csrc/*.hpp) and
+# how many instantiations of each the launchers use: a header dropped from the unit, or a
+# launcher that lost a variant, fails here.
+KERNELS = {
+    "seg_kernel": 2, "reas_kernel": 3, "reas_classify_kernel": 1, "reas_scatter_kernel": 6,
+    "reas_scatter_classify_kernel": 6, "ro_key_kernel": 1, "ro_place_kernel": 1, "ro_walk_kernel": 1,
+    "zero_words_kernel": 1, "fill_bytes_kernel": 1, "copy_spans_kernel": 1, "reas_gc_kernel": 1,
+    "reas_recycle_kernel": 1, "reas_compact_kernel": 1, "reas_compact_finish": 1, "relay_plan_kernel": 1,
+    "route_hist_kernel": 1, "route_scan_kernel": 1, "route_pack_kernel": 1, "route_append_kernel": 1,
+}
+assert sum(KERNELS.values()) == 33
 
 
 def _remarks(src, tmp_path):
@@ -43,3 +54,7 @@ def test_no_scratch_no_spills(src, tmp_path):
     bad = {k: v for k, v in kernels.items()
            if v.get("ScratchSize", 0) or v.get("VGPRs Spill", 0) or v.get("SGPRs Spill", 0)}
     assert not bad, f"kernels with scratch or spills: {bad}"
+    # mangled names: e2sar_amd::NAME is ...9e2sar_amd<len(NAME)>NAME...
+    found = {n: sum(f"9e2sar_amd{len(n)}{n}" in k for k in kernels) for n in KERNELS}
+    missing = {n: (found[n], want) for n, want in KERNELS.items() if found[n] < want}
+    assert not missing, f"kernels missing from the translation unit (found, expected): {missing}"

@@ -23,13 +23,15 @@ for f in os.listdir(src):
     if f.endswith((".hip", ".hpp", ".cpp")):
         shutil.copy(os.path.join(src, f), dst)
 p = os.path.join(dst, "sar_kernels.hip")
-s = open(p).read()
+# the one translation unit and the headers that hold its device code
+texts = {f: open(os.path.join(dst, f)).read() for f in os.listdir(dst) if f.endswith((".hip", ".hpp"))}
 
 
 def sub(old, new):
-    global s
-    assert old in s, old
-    s = s.replace(old, new)
+    """Replace old, which exactly one of the copied files holds."""
+    hits = [f for f, s in texts.items() if old in s]
+    assert len(hits) == 1, (old, hits)
+    texts[hits[0]] = texts[hits[0]].replace(old, new)
 
 
 sub("constexpr int kReasU = 4;", "constexpr int kReasU = 4;\nconstexpr int kReasUOne = %d;" % U)
@@ -56,17 +58,21 @@ sub("constexpr int kReasNTSmall = 768;", "constexpr int kReasNTSmall = %d;" % nt
 sub("""    const uint32_t spc = stride >> 4, budget = kReasChunksPerBlock;
     uint32_t G = 64;
     while (G > 1 && G * spc > budget) G >>= 1;""", """    const uint32_t spc = stride >> 4,
-                   budget = NT == kReasNTSmall ? (uint32_t)(kReasUOne * kReasNTSmall) : kReasChunksPerBlock;
+                   budget = small ? (uint32_t)(kReasUOne * kReasNTSmall) : kReasChunksPerBlock;
     uint32_t G = 64;
     while (G > 1 && G * spc > budget) G >>= 1;
-    if (NT == kReasNTSmall) G = budget / spc < 64u ? (budget / spc ? budget / spc : 1u) : 64u;""")
-sub("if (c > 64 || 4u * c < 3u * G0 || 3u * c > 4u * G0) continue;",
-    "if (c > 64 || c * spc > budget || 4u * c < 3u * G0 || 3u * c > 4u * G0) continue;")
-sub("""    const uint32_t cap = NT == kReasNTSmall ? reas_resident_groups<U, kReasNTSmall>()""",
-    """    const uint32_t cap = NT == kReasNTSmall ? reas_resident_groups<kReasUOne, kReasNTSmall>()""")
+    if (small) G = budget / spc < 64u ? (budget / spc ? budget / spc : 1u) : 64u;""")
+sub("""    if (fixedG) return fixedG < 64u ? fixedG : 64u;
+""", """    if (fixedG) return fixedG < 64u ? fixedG : 64u;
+    const bool small = resident == &reas_resident_groups<kReasUOne, kReasNTSmall>;
+""")
+sub("return balance_waves(n, G, resident(), 64u);",
+    "return balance_waves(n, G, resident(), std::min<uint32_t>(64u, std::max<uint32_t>(1u, budget / spc)));")
+sub("""small ? reas_resident_groups<U, kReasNTSmall>""", """small ? reas_resident_groups<kReasUOne, kReasNTSmall>""")
 sub("""        hipLaunchKernelGGL((reas_kernel<U, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,""",
     """        hipLaunchKernelGGL((reas_kernel<kReasUOne, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,""")
-open(p, "w").write(s)
+for f, s in texts.items():
+    open(os.path.join(dst, f), "w").write(s)
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Iinclude", "-I" + dst,
        "-shared", "-o", os.path.join(root, "build/variants/lib_%s.so" % name),
        p, os.path.join(dst, "capi.cpp")]
