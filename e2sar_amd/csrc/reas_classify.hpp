@@ -148,6 +148,14 @@ __device__ Classified classify_wave(const ReasDev &R, const RawHdr &raw, uint32_
         ev = 0;
         d = off = blen = pl = 0;
     }
+    // bounds against the fragment's own bufferLength, before the lookup, as the
+    // reference-order key pass has it: a fragment that overruns what its own header
+    // announces creates no item (it used to claim a slot and a buffer that only the GC freed,
+    // as a lost event of 0 fragments)
+    if (ok && (uint64_t)off + pl > blen) {
+        ok = false;
+        derr = true;
+    }
 
     // ---- runs of equal keys ----
     const uint64_t pev = ((uint64_t)lane_prev((uint32_t)(ev >> 32), 0u) << 32) | lane_prev((uint32_t)ev, 0u);

@@ -305,7 +305,9 @@ int e2sar_hip_reas_get_stats(e2sar_hip_reas *r, e2sar_hip_reas_stats *out);
 /* Recycle the arena and the event table.  Only legal when no event is in progress
  * and every completed record has been polled (else E2SAR_HIP_ERR_LOGIC); the caller
  * promises it no longer reads event bytes from the arena.  `force` drops in-progress
- * events without logging them.  Asynchronous. */
+ * events without logging them.  It also discards completed records not yet polled (the
+ * bench's step relies on that); lost records not yet polled and the statistics stay.
+ * Asynchronous. */
 int e2sar_hip_reas_recycle(e2sar_hip_reas *r, int force, void *stream);
 /* e2sar_hip_segment_batch and e2sar_hip_reas_recycle(r, force) in ONE launch: extra
  * workgroups at the end of the segmentation grid reset r's table and arena (no seg block

@@ -18,7 +18,9 @@ def test_copy_spans_device_to_device(hip):
     spans, checks = [], []
     total = sum(SIZES) * 2 + 64 * 4096
     src = torch.from_numpy(rng.integers(0, 256, total, dtype=np.uint8)).to(hip.torch_device)
-    dst = torch.zeros(sum(SIZES) * 7 + 77 * 8 + 4096, dtype=torch.uint8, device=hip.torch_device)
+    # a non-zero pattern under the destinations: a store past a span's end would show
+    before = (np.arange(sum(SIZES) * 7 + 77 * 8 + 4096) * 37 % 251 + 1).astype(np.uint8)
+    dst = torch.from_numpy(before).to(hip.torch_device)
     so = do = 0
     for k, n in enumerate(SIZES * 7):                  # 77 spans: two launches
         sa, da = so + (k % 3) * 4, do + (k % 5)          # aligned and misaligned both sides
@@ -29,8 +31,14 @@ def test_copy_spans_device_to_device(hip):
     hip.copy_spans(spans)
     torch.cuda.synchronize()
     hs, hd = src.cpu().numpy(), dst.cpu().numpy()
+    outside = np.ones(len(hd), bool)
     for sa, da, n in checks:
         assert np.array_equal(hd[da:da + n], hs[sa:sa + n]), (sa, da, n)
+        outside[da:da + n] = False
+    # every byte outside the 77 spans -- the 1-byte gaps between them, the area after the
+    # last -- still holds the pattern
+    assert outside.sum() >= 77 + 4096 and not outside[[da + n - 1 for _, da, n in checks if n]].any()
+    assert np.array_equal(hd[outside], before[outside])
 
 
 def test_copy_spans_device_to_pinned_host(hip):
