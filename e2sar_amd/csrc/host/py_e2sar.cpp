@@ -86,7 +86,7 @@ PYBIND11_MODULE(e2sar_py, m)
     m.attr("_udphdr_len") = py::int_(UDP_HDRLEN);
     m.attr("_total_hdr_len") = py::int_(TOTAL_HDR_LEN);
     m.attr("_rehdr_version_nibble") = py::int_(rehdrVersionNibble);
-    m.def("get_version", []() { return std::string("0.3.2-mi355x"); });
+    m.def("get_version", []() { return std::string(get_Version()); });
     m.def("_get_PortRange", &get_PortRange, py::arg("source_count"));   // e2sarCP.hpp:772-798
 
     py::enum_<E2SARErrorc>(m, "E2SARErrorc")

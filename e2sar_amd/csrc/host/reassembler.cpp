@@ -12,11 +12,8 @@
 // that getEvent/recvEvent hand over.  Lost-event records are drained the same way; the
 // device GC pass runs every eventTimeout_ms; the table and arena are recycled or compacted
 // when either passes half full.
-#include <arpa/inet.h>
-#include <netinet/in.h>
 #include <poll.h>
 #include <sys/socket.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -33,12 +30,9 @@
 
 namespace e2sar {
 
-using detail::hip_error;
-
 struct Reassembler::Impl {
     EjfatURI uri;
     ReassemblerFlags flags;
-    std::vector<int> cores;
     std::string dataIP;
     bool v6 = false;
     uint16_t dataPort;
@@ -48,39 +42,45 @@ struct Reassembler::Impl {
     std::vector<std::vector<uint16_t>> threadsToPorts;
 
     // device: the compute stream (the context's) and a copy stream; two device datagram
-    // buffers so batch b+1 is copied in while batch b is reassembled
-    e2sar_hip_ctx *ctx = nullptr;
-    void *stream = nullptr;
-    void *copyStream = nullptr;
-    e2sar_hip_reas *reas = nullptr;
+    // buffers so batch b+1 is copied in while batch b is reassembled.
+    // Teardown is the reverse of this declaration order, from `batches` up to `copyStream`:
+    // ~Impl first synchronises both streams; then the pinned batches and staging, the
+    // reassembler, the device sets and the events go, all before the context; the context is
+    // destroyed while its stream is alive (e2sar_hip_ctx_destroy synchronises it); the
+    // streams go last.
+    detail::Stream copyStream;
+    detail::Stream stream;
+    detail::Ctx ctx;
+    detail::Event gatherDone;           // recorded on the compute stream after a drain's gather
     struct DevSet {
-        uint8_t *pkts = nullptr;
-        uint32_t *lens = nullptr;
-        void *h2dDone = nullptr;        // recorded on the copy stream after the batch's copy
+        detail::DeviceBuf<uint8_t> pkts;
+        detail::DeviceBuf<uint32_t> lens;
+        detail::Event h2dDone;          // recorded on the copy stream after the batch's copy
     };
     DevSet sets[2];
-    void *gatherDone = nullptr;         // recorded on the compute stream after a drain's gather
-    uint8_t *stage = nullptr;           // pinned staging for completed events
+    detail::Reas reas;
+    detail::Pinned<uint8_t> stage;      // pinned staging for completed events
     size_t stageBytes = 0;
+    struct Batch {                      // a datagram batch (pinned)
+        detail::Pinned<uint8_t> pkts;
+        detail::Pinned<uint32_t> lens;
+        uint32_t n = 0;
+    };
+    std::vector<Batch> batches;
+
     std::vector<size_t> stageOffs;      // staging offsets of the records of the gather in flight
     std::atomic<uint64_t> upkeeps{0};   // recycles + compactions done
     std::vector<e2sar_hip_event_rec> recs;
     std::vector<e2sar_hip_lost_rec> lrecs;
 
-    // datagram batches (pinned)
-    struct Batch {
-        uint8_t *pkts = nullptr;
-        uint32_t *lens = nullptr;
-        uint32_t n = 0;
-    };
-    std::vector<Batch> batches;
+    // queues of datagram batches between the receive threads and the device thread
     std::mutex bMu;
     std::condition_variable bFreeCv, bFullCv;
     std::deque<Batch *> freeB, fullB;
 
     // event queue (hpp:126-127: unbounded, see gatherFinish) and lost events (hpp:102-122, 262-279)
     struct Ev {
-        uint8_t *event;
+        std::unique_ptr<uint8_t[]> event;      // released to the caller of getEvent/recvEvent
         size_t bytes;
         EventNum_t eventNum;
         uint16_t dataId;
@@ -93,7 +93,7 @@ struct Reassembler::Impl {
     std::set<std::pair<EventNum_t, uint16_t>> lostSeen;
 
     // host-side counters
-    std::atomic<uint64_t> hostEnqueueLoss{0}, hostReassemblyLoss{0};
+    std::atomic<uint64_t> hostEnqueueLoss{0};
     std::atomic<int> lastErrno{0}, dataErrCnt{0};
     std::atomic<E2SARErrorc> lastErr{E2SARErrorc::NoError};
     std::map<uint16_t, std::atomic<size_t> *> perPort;
@@ -107,14 +107,20 @@ struct Reassembler::Impl {
     e2sar_hip_reas_stats lastStats{};
     std::mutex sMu;
 
-    Impl(const EjfatURI &u, const ReassemblerFlags &f) : uri(u), flags(f) {}
+    Impl(const EjfatURI &u, const ReassemblerFlags &f, const std::string &ip, uint16_t port)
+        : uri(u), flags(f), dataIP(ip), v6(ip.find(':') != std::string::npos), dataPort(port)
+    {
+    }
     ~Impl();
     void setup(size_t nThreads);
-    void recvBody(size_t t, std::vector<int> fds, std::vector<uint16_t> ports);
+    void recvBody(const std::vector<detail::Fd> &fds, const std::vector<uint16_t> &ports);
     void devBody();
     void drainLost();
     uint32_t gatherLaunch(uint32_t first, uint32_t n, uint8_t *arena);
     void gatherFinish(uint32_t first, uint32_t upto);
+    void gatherAll(uint32_t launched, uint32_t n, uint8_t *arena);
+    int popEvent(uint8_t **event, size_t *bytes, EventNum_t *eventNum, uint16_t *dataId);
+    e2sar_hip_reas_stats deviceStats();
     bool needsUpkeep(const e2sar_hip_reas_stats &st) const;
     void upkeep(const e2sar_hip_reas_stats &st);
     Batch *takeFree();
@@ -125,28 +131,9 @@ struct Reassembler::Impl {
 Reassembler::Impl::~Impl()
 {
     if (ctx) {
-        e2sar_hip_stream_sync(ctx, stream);
-        e2sar_hip_stream_sync(ctx, copyStream);
+        e2sar_hip_stream_sync(ctx.get(), stream.get());
+        e2sar_hip_stream_sync(ctx.get(), copyStream.get());
     }
-    for (auto &b : batches) {
-        if (b.pkts) e2sar_hip_host_free(b.pkts);
-        if (b.lens) e2sar_hip_host_free(b.lens);
-    }
-    if (stage) e2sar_hip_host_free(stage);
-    if (reas) e2sar_hip_reas_destroy(reas);
-    if (ctx) {
-        for (auto &d : sets) {
-            if (d.pkts) e2sar_hip_device_free(ctx, d.pkts);
-            if (d.lens) e2sar_hip_device_free(ctx, d.lens);
-            e2sar_hip_event_destroy(d.h2dDone);
-        }
-        e2sar_hip_event_destroy(gatherDone);
-        e2sar_hip_ctx_destroy(ctx);
-    }
-    if (stream) e2sar_hip_stream_destroy(stream);
-    if (copyStream) e2sar_hip_stream_destroy(copyStream);
-    std::lock_guard<std::mutex> lk(eMu);
-    for (auto &e : evq) delete[] e.event;
 }
 
 // ctor body: port range and thread/port assignment (cpp:37-181, hpp:308-318)
@@ -168,9 +155,9 @@ void Reassembler::Impl::setup(size_t nThreads)
         perPort[(uint16_t)(dataPort + i)] = perPortStore.back().get();
     }
 
-    int rc = e2sar_hip_stream_create(flags.gpuDevice, &stream);
-    if (rc == 0) rc = e2sar_hip_stream_create(flags.gpuDevice, &copyStream);
-    if (rc == 0) rc = e2sar_hip_ctx_create(flags.gpuDevice, stream, &ctx);
+    int rc = detail::make(stream, e2sar_hip_stream_create, flags.gpuDevice);
+    if (rc == 0) rc = detail::make(copyStream, e2sar_hip_stream_create, flags.gpuDevice);
+    if (rc == 0) rc = detail::make(ctx, e2sar_hip_ctx_create, flags.gpuDevice, stream.get());
     e2sar_hip_reas_config cfg{};
     cfg.withLBHeader = flags.withLBHeader ? 1 : 0;
     cfg.tableSlots = flags.tableSlots;
@@ -178,15 +165,15 @@ void Reassembler::Impl::setup(size_t nThreads)
     cfg.lostCapacity = 4096;
     cfg.arenaBytes = flags.arenaBytes;
     cfg.flags = E2SAR_HIP_REAS_COMPACTABLE | (flags.referenceOrder ? E2SAR_HIP_REAS_REFERENCE_ORDER : 0u);
-    if (rc == 0) rc = e2sar_hip_reas_create(ctx, &cfg, &reas);
+    if (rc == 0) rc = detail::make(reas, e2sar_hip_reas_create, ctx.get(), &cfg);
     for (auto &d : sets) {
-        if (rc == 0) rc = e2sar_hip_device_alloc(ctx, flags.recvBatch * flags.recvStride, reinterpret_cast<void **>(&d.pkts));
-        if (rc == 0) rc = e2sar_hip_device_alloc(ctx, flags.recvBatch * 4, reinterpret_cast<void **>(&d.lens));
-        if (rc == 0) rc = e2sar_hip_event_create(ctx, &d.h2dDone);
+        if (rc == 0) rc = detail::alloc_device(ctx.get(), flags.recvBatch * flags.recvStride, d.pkts);
+        if (rc == 0) rc = detail::alloc_device(ctx.get(), flags.recvBatch, d.lens);
+        if (rc == 0) rc = detail::make(d.h2dDone, e2sar_hip_event_create, ctx.get());
     }
-    if (rc == 0) rc = e2sar_hip_event_create(ctx, &gatherDone);
+    if (rc == 0) rc = detail::make(gatherDone, e2sar_hip_event_create, ctx.get());
     stageBytes = std::max<size_t>(size_t(64) << 20, 2 * flags.recvBatch * flags.recvStride);
-    if (rc == 0) rc = e2sar_hip_host_alloc(stageBytes, reinterpret_cast<void **>(&stage));
+    if (rc == 0) rc = detail::alloc_pinned(stageBytes, stage);
     // host batches: two per receive thread being filled / queued, two on their way to the
     // device, and slack so a receive thread never waits for one while the device thread
     // still holds batches whose copies are done but not yet handed back (MTU 9000 loopback
@@ -194,8 +181,8 @@ void Reassembler::Impl::setup(size_t nThreads)
     const size_t nb = 2 * numRecvThreads + 6;
     batches.resize(nb);
     for (auto &b : batches) {
-        if (rc == 0) rc = e2sar_hip_host_alloc(flags.recvBatch * flags.recvStride, reinterpret_cast<void **>(&b.pkts));
-        if (rc == 0) rc = e2sar_hip_host_alloc(flags.recvBatch * 4, reinterpret_cast<void **>(&b.lens));
+        if (rc == 0) rc = detail::alloc_pinned(flags.recvBatch * flags.recvStride, b.pkts);
+        if (rc == 0) rc = detail::alloc_pinned(flags.recvBatch, b.lens);
         freeB.push_back(&b);
     }
     if (rc) throw E2SARException(std::string("Unable to set up the GPU reassembler: ") + e2sar_hip_last_error());
@@ -203,47 +190,25 @@ void Reassembler::Impl::setup(size_t nThreads)
     lrecs.resize(cfg.lostCapacity);
 }
 
+// the one initialiser: the three other constructors delegate to this one
 Reassembler::Reassembler(const EjfatURI &uri, const std::string &data_ip, uint16_t starting_port,
-                         std::vector<int> cpuCoreList, const ReassemblerFlags &rflags)
-    : impl(new Impl(uri, rflags))
+                         size_t numRecvThreads, const ReassemblerFlags &rflags)
+    : impl(new Impl(uri, rflags, data_ip, starting_port))
 {
-    impl->dataIP = data_ip;
-    impl->v6 = data_ip.find(':') != std::string::npos;
-    impl->dataPort = starting_port;
-    impl->cores = cpuCoreList;
-    impl->setup(cpuCoreList.size());
+    impl->setup(numRecvThreads);
 }
 
 Reassembler::Reassembler(const EjfatURI &uri, const std::string &data_ip, uint16_t starting_port,
-                         size_t numRecvThreads, const ReassemblerFlags &rflags)
-    : impl(new Impl(uri, rflags))
-{
-    impl->dataIP = data_ip;
-    impl->v6 = data_ip.find(':') != std::string::npos;
-    impl->dataPort = starting_port;
-    impl->setup(numRecvThreads);
-}
+                         std::vector<int> cpuCoreList, const ReassemblerFlags &rflags)
+    : Reassembler(uri, data_ip, starting_port, cpuCoreList.size(), rflags) {}
 
 Reassembler::Reassembler(const EjfatURI &uri, uint16_t starting_port, std::vector<int> cpuCoreList,
                          const ReassemblerFlags &rflags, bool v6)
-    : impl(new Impl(uri, rflags))
-{
-    impl->dataIP = v6 ? "::" : "0.0.0.0";
-    impl->v6 = v6;
-    impl->dataPort = starting_port;
-    impl->cores = cpuCoreList;
-    impl->setup(cpuCoreList.size());
-}
+    : Reassembler(uri, std::string(v6 ? "::" : "0.0.0.0"), starting_port, cpuCoreList.size(), rflags) {}
 
 Reassembler::Reassembler(const EjfatURI &uri, uint16_t starting_port, size_t numRecvThreads,
                          const ReassemblerFlags &rflags, bool v6)
-    : impl(new Impl(uri, rflags))
-{
-    impl->dataIP = v6 ? "::" : "0.0.0.0";
-    impl->v6 = v6;
-    impl->dataPort = starting_port;
-    impl->setup(numRecvThreads);
-}
+    : Reassembler(uri, std::string(v6 ? "::" : "0.0.0.0"), starting_port, numRecvThreads, rflags) {}
 
 Reassembler::~Reassembler() { stopThreads(); }
 
@@ -258,11 +223,42 @@ Reassembler::Impl::Batch *Reassembler::Impl::takeFree()
     return b;
 }
 
+// E2SAR_RECV_SPIN_US: how long a receive thread stays awake after its last datagram
+static uint64_t recv_spin_us()
+{
+    static const char *const v = getenv("E2SAR_RECV_SPIN_US");
+    return v ? (uint64_t)strtoull(v, nullptr, 10) : 200ull;
+}
+
+// E2SAR_RECV_PROFILE=1: where the receive and device threads' time goes (stderr at exit).
+// lap(bucket) charges the time since start() or the previous lap to `bucket`; report() prints
+// the run time and the given fields.  With the profile off, each is only a branch.
+struct LapClock {
+    const bool on = [] {
+        static const bool e = getenv("E2SAR_RECV_PROFILE") != nullptr;
+        return e;
+    }();
+    const uint64_t t0 = on ? detail::now_us() : 0;
+    uint64_t last = t0;
+    void start() { last = on ? detail::now_us() : 0; }
+    void lap(uint64_t &bucket)
+    {
+        if (!on) return;
+        const uint64_t t = detail::now_us();
+        bucket += t - last;
+        last = t;
+    }
+    template <class... A> void report(const char *fmt, A... fields) const
+    {
+        if (on) fprintf(stderr, fmt, (detail::now_us() - t0) * 1e-6, fields...);
+    }
+};
+
 // The receive loop: select/recvfrom (cpp:293-333) become poll + recvmmsg into a batch.
-void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint16_t> ports)
+void Reassembler::Impl::recvBody(const std::vector<detail::Fd> &fds, const std::vector<uint16_t> &ports)
 {
     std::vector<pollfd> pf(fds.size());
-    for (size_t i = 0; i < fds.size(); i++) pf[i] = pollfd{fds[i], POLLIN, 0};
+    for (size_t i = 0; i < fds.size(); i++) pf[i] = pollfd{fds[i].get(), POLLIN, 0};
     const size_t cap = flags.recvBatch;
     const size_t S = flags.recvStride;
     std::vector<mmsghdr> mv(cap);
@@ -273,7 +269,7 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
     auto vectorFor = [&](const Batch *x) {
         if (vecFor == x) return;
         for (size_t k = 0; k < cap; k++) {
-            iv[k].iov_base = x->pkts + k * S;
+            iv[k].iov_base = x->pkts.get() + k * S;
             iv[k].iov_len = S;
             mv[k].msg_hdr = msghdr{};
             mv[k].msg_hdr.msg_iov = &iv[k];
@@ -281,13 +277,9 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
         }
         vecFor = x;
     };
-    // E2SAR_RECV_PROFILE=1: where the receive thread's time goes (stderr at exit)
-    static const bool prof = getenv("E2SAR_RECV_PROFILE") != nullptr;
-    uint64_t tPoll = 0, tRecv = 0, tFree = 0, nCalls = 0, nDg = 0, nFlush = 0, tLastDg = 0, t0 = detail::now_us();
-    static const uint64_t spinUs = [] {
-        const char *v = getenv("E2SAR_RECV_SPIN_US");
-        return v ? (uint64_t)strtoull(v, nullptr, 10) : 200ull;
-    }();
+    LapClock clk;
+    uint64_t tPoll = 0, tRecv = 0, tFree = 0, nCalls = 0, nDg = 0, nFlush = 0, tLastDg = 0;
+    const uint64_t spinUs = recv_spin_us();
     uint64_t lastData = 0;
     Batch *b = takeFree();
     uint64_t firstUs = 0;
@@ -298,9 +290,9 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
             fullB.push_back(b);
         }
         bFullCv.notify_one();
-        const uint64_t a = prof ? detail::now_us() : 0;
+        clk.start();
         b = takeFree();
-        if (prof) tFree += detail::now_us() - a, nFlush++;
+        clk.lap(tFree), nFlush++;
         firstUs = 0;
     };
     while (!stop) {
@@ -317,9 +309,9 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
             for (auto &p : pf) p.revents = POLLIN;
             pr = (int)pf.size();
         } else {
-            const uint64_t pa = prof ? detail::now_us() : 0;
+            clk.start();
             pr = poll(pf.data(), pf.size(), timeout);
-            if (prof) tPoll += detail::now_us() - pa;
+            clk.lap(tPoll);
         }
         if (pr < 0) {
             if (errno != EINTR) {
@@ -334,12 +326,10 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
                 const size_t room = cap - b->n;
                 vectorFor(b);
                 mmsghdr *const m = mv.data() + b->n;
-                const uint64_t ra = prof ? detail::now_us() : 0;
-                const int r = recvmmsg(fds[i], m, (unsigned)room, MSG_DONTWAIT, nullptr);
-                if (prof) {
-                    tRecv += detail::now_us() - ra, nCalls++, nDg += r > 0 ? (uint64_t)r : 0u;
-                    if (r > 0) tLastDg = detail::now_us() - t0;
-                }
+                clk.start();
+                const int r = recvmmsg(fds[i].get(), m, (unsigned)room, MSG_DONTWAIT, nullptr);
+                clk.lap(tRecv), nCalls++;
+                if (r > 0) nDg += (uint64_t)r, tLastDg = clk.last - clk.t0;
                 if (r < 0) {
                     if (errno != EAGAIN && errno != EWOULDBLOCK && errno != EINTR) {
                         dataErrCnt++;
@@ -365,18 +355,14 @@ void Reassembler::Impl::recvBody(size_t, std::vector<int> fds, std::vector<uint1
         // device -- and gained nothing at 1500)
         if (b && b->n > 0 && detail::now_us() - firstUs >= (uint64_t)flags.batchTimeout_us) flush();
     }
-    if (prof)
-        fprintf(stderr, "recv thread: %.3f s, poll %.3f s, recvmmsg %.3f s (%llu calls, %llu datagrams), "
-                        "waiting for a free batch %.3f s (%llu batches), last datagram at %.3f s\n",
-                (detail::now_us() - t0) * 1e-6, tPoll * 1e-6, tRecv * 1e-6, (unsigned long long)nCalls,
-                (unsigned long long)nDg, tFree * 1e-6, (unsigned long long)nFlush, tLastDg * 1e-6);
+    clk.report("recv thread: %.3f s, poll %.3f s, recvmmsg %.3f s (%llu calls, %llu datagrams), "
+               "waiting for a free batch %.3f s (%llu batches), last datagram at %.3f s\n",
+               tPoll * 1e-6, tRecv * 1e-6, (unsigned long long)nCalls, (unsigned long long)nDg, tFree * 1e-6,
+               (unsigned long long)nFlush, tLastDg * 1e-6);
     if (b) {
-        if (b->n) {
+        {
             std::lock_guard<std::mutex> lk(bMu);
-            fullB.push_back(b);
-        } else {
-            std::lock_guard<std::mutex> lk(bMu);
-            freeB.push_back(b);
+            (b->n ? fullB : freeB).push_back(b);
         }
         bFullCv.notify_one();
     }
@@ -416,11 +402,9 @@ uint32_t Reassembler::Impl::gatherLaunch(uint32_t first, uint32_t n, uint8_t *ar
         const size_t b = recs[i].bytes;
         const size_t need = (b + 63) & ~(size_t)63;
         if (need > stageBytes && i == first) {          // larger than all of the staging: grow it
-            e2sar_hip_stream_sync(ctx, stream);
-            e2sar_hip_host_free(stage);
-            stage = nullptr;
+            e2sar_hip_stream_sync(ctx.get(), stream.get());   // no gather is writing the old one
             stageBytes = 0;
-            if (e2sar_hip_host_alloc(need, reinterpret_cast<void **>(&stage)) != 0) {
+            if (detail::alloc_pinned(need, stage) != 0) {
                 lastErr = E2SARErrorc::MemoryError;
                 return n;
             }
@@ -428,11 +412,11 @@ uint32_t Reassembler::Impl::gatherLaunch(uint32_t first, uint32_t n, uint8_t *ar
         }
         if (used + need > stageBytes) break;
         stageOffs.push_back(used);
-        if (b) spans.push_back(e2sar_hip_copy_span{arena + recs[i].arenaOffset, stage + used, b});
+        if (b) spans.push_back(e2sar_hip_copy_span{arena + recs[i].arenaOffset, stage.get() + used, b});
         used += need;
     }
-    int rc = e2sar_hip_copy_spans(ctx, spans.data(), (uint32_t)spans.size(), stream);
-    if (rc == 0) rc = e2sar_hip_event_record(ctx, gatherDone, stream);
+    int rc = e2sar_hip_copy_spans(ctx.get(), spans.data(), (uint32_t)spans.size(), stream.get());
+    if (rc == 0) rc = e2sar_hip_event_record(ctx.get(), gatherDone.get(), stream.get());
     if (rc) lastErr = E2SARErrorc::SystemError;
     return i;
 }
@@ -440,7 +424,7 @@ uint32_t Reassembler::Impl::gatherLaunch(uint32_t first, uint32_t n, uint8_t *ar
 void Reassembler::Impl::gatherFinish(uint32_t first, uint32_t upto)
 {
     if (upto <= first) return;
-    if (e2sar_hip_event_sync(gatherDone) != 0 || stageOffs.size() != upto - first) {
+    if (e2sar_hip_event_sync(gatherDone.get()) != 0 || stageOffs.size() != upto - first) {
         lastErr = E2SARErrorc::SystemError;
         return;
     }
@@ -457,32 +441,42 @@ void Reassembler::Impl::gatherFinish(uint32_t first, uint32_t upto)
     ready.reserve(upto - first);
     for (uint32_t k = first; k < upto; k++) {
         const auto &r = recs[k];
-        auto *buf = new (std::nothrow) uint8_t[r.bytes ? r.bytes : 1];
+        std::unique_ptr<uint8_t[]> buf(new (std::nothrow) uint8_t[r.bytes ? r.bytes : 1]);
         if (!buf) {
             lose(r.eventNum, r.dataId);
             continue;
         }
-        if (r.bytes) memcpy(buf, stage + stageOffs[k - first], r.bytes);
-        ready.push_back(Ev{buf, r.bytes, r.eventNum, r.dataId});
+        if (r.bytes) memcpy(buf.get(), stage.get() + stageOffs[k - first], r.bytes);
+        ready.push_back(Ev{std::move(buf), r.bytes, r.eventNum, r.dataId});
     }
     {
         std::lock_guard<std::mutex> lk(eMu);
         for (auto &e : ready) {
             try {
-                evq.push_back(e);
+                evq.push_back(std::move(e));
             } catch (const std::bad_alloc &) {
-                lose(e.eventNum, e.dataId);
-                delete[] e.event;
+                lose(e.eventNum, e.dataId);     // e keeps its buffer, which goes with `ready`
             }
         }
     }
     eCv.notify_all();
 }
 
+// Records [0, launched) are in the gather in flight: finish it, then launch and finish
+// gathers until all n polled records have left the arena.
+void Reassembler::Impl::gatherAll(uint32_t launched, uint32_t n, uint8_t *arena)
+{
+    gatherFinish(0, launched);
+    for (uint32_t done = launched, upto; done < n; done = upto) {
+        upto = gatherLaunch(done, n, arena);
+        gatherFinish(done, upto);
+    }
+}
+
 void Reassembler::Impl::drainLost()
 {
     uint32_t nl = 0;
-    if (e2sar_hip_reas_lost_poll(reas, lrecs.data(), (uint32_t)lrecs.size(), &nl) == 0 && nl) {
+    if (e2sar_hip_reas_lost_poll(reas.get(), lrecs.data(), (uint32_t)lrecs.size(), &nl) == 0 && nl) {
         std::lock_guard<std::mutex> l2(lMu);
         for (uint32_t i = 0; i < nl; i++) {   // logLostEvent dedupe (hpp:266-269)
             const auto &l = lrecs[i];
@@ -507,7 +501,7 @@ bool Reassembler::Impl::needsUpkeep(const e2sar_hip_reas_stats &st) const
 
 void Reassembler::Impl::upkeep(const e2sar_hip_reas_stats &st)
 {
-    const int rc = st.inProgress == 0 ? e2sar_hip_reas_recycle(reas, 0, nullptr) : e2sar_hip_reas_compact(reas, nullptr);
+    const int rc = st.inProgress == 0 ? e2sar_hip_reas_recycle(reas.get(), 0, nullptr) : e2sar_hip_reas_compact(reas.get(), nullptr);
     if (rc) lastErr = static_cast<E2SARErrorc>(-rc);
     else upkeeps++;
 }
@@ -523,14 +517,15 @@ void Reassembler::Impl::devBody()
     const uint32_t stride = (uint32_t)flags.recvStride;
     bool kernelInFlight = false;       // a launched batch whose results are not yet drained
     int cur = 0;                       // device set of the next copy
-    static const bool prof = getenv("E2SAR_RECV_PROFILE") != nullptr;
-    uint64_t pT0 = detail::now_us(), pWait = 0, pPoll = 0, pGather = 0, pUpkeep = 0, pLaunch = 0, pCycles = 0,
-             pBatches = 0, pDg = 0, pEvents = 0, pLastEv = 0;
-    auto tick = [&]() { return prof ? detail::now_us() : 0; };
+    e2sar_hip_ctx *const c = ctx.get();
+    e2sar_hip_reas *const r = reas.get();
+    LapClock clk;
+    uint64_t pWait = 0, pPoll = 0, pGather = 0, pUpkeep = 0, pLaunch = 0, pCycles = 0, pBatches = 0, pDg = 0, pEvents = 0,
+             pLastEv = 0;
     while (true) {
-        uint64_t ta = tick();
+        clk.start();
         Batch *b = takeFull(!kernelInFlight);
-        if (prof) pWait += tick() - ta, pCycles++, pBatches += b ? 1 : 0, pDg += b ? b->n : 0;
+        clk.lap(pWait), pCycles++, pBatches += b ? 1 : 0, pDg += b ? b->n : 0;
         if (!b && !kernelInFlight && stop && recvActive.load() == 0) {
             std::lock_guard<std::mutex> lk(bMu);
             if (fullB.empty()) break;
@@ -541,77 +536,61 @@ void Reassembler::Impl::devBody()
         if (b) {
             bn = b->n;
             bnow = detail::steady_ms();
-            int rc = e2sar_hip_memcpy_async(ctx, d.pkts, b->pkts, (size_t)b->n * stride, 0, copyStream);
-            if (rc == 0) rc = e2sar_hip_memcpy_async(ctx, d.lens, b->lens, (size_t)b->n * 4, 0, copyStream);
-            if (rc == 0) rc = e2sar_hip_event_record(ctx, d.h2dDone, copyStream);
+            int rc = e2sar_hip_memcpy_async(c, d.pkts.get(), b->pkts.get(), (size_t)b->n * stride, 0, copyStream.get());
+            if (rc == 0) rc = e2sar_hip_memcpy_async(c, d.lens.get(), b->lens.get(), (size_t)b->n * 4, 0, copyStream.get());
+            if (rc == 0) rc = e2sar_hip_event_record(c, d.h2dDone.get(), copyStream.get());
             if (rc) lastErr = static_cast<E2SARErrorc>(-rc);
         }
         uint32_t n = 0;
-        ta = tick();
-        if (e2sar_hip_reas_poll(reas, recs.data(), (uint32_t)recs.size(), &n) != 0) lastErr = E2SARErrorc::SystemError;
-        if (prof) pPoll += tick() - ta, pEvents += n, pLastEv = n ? tick() - pT0 : pLastEv;
+        clk.start();
+        if (e2sar_hip_reas_poll(r, recs.data(), (uint32_t)recs.size(), &n) != 0) lastErr = E2SARErrorc::SystemError;
+        clk.lap(pPoll), pEvents += n;
+        if (n) pLastEv = clk.last - clk.t0;
         if (b) giveBack(b);                                   // its bytes are on the device now
         kernelInFlight = false;
         e2sar_hip_reas_stats st{};
-        const bool haveStats = e2sar_hip_reas_get_stats(reas, &st) == 0;
+        const bool haveStats = e2sar_hip_reas_get_stats(r, &st) == 0;
         if (haveStats) {
             std::lock_guard<std::mutex> lk(sMu);
             lastStats = st;
         }
-        uint8_t *arena = e2sar_hip_reas_arena(reas);
-        uint32_t upto = n ? gatherLaunch(0, n, arena) : 0;
+        uint8_t *arena = e2sar_hip_reas_arena(r);
+        const uint32_t launched = n ? gatherLaunch(0, n, arena) : 0;
         const uint64_t now = detail::steady_ms();
         const bool gcDue = now - lastGc >= (uint64_t)flags.eventTimeout_ms;
         const bool upkeepDue = haveStats && needsUpkeep(st);
-        uint32_t done = 0;
-        ta = tick();
+        bool gathered = n == 0;
+        clk.start();
         if (gcDue || upkeepDue) {
             // every completed event leaves the arena before the GC pass, a recycle or a compaction
-            for (gatherFinish(0, upto), done = upto; done < n; done = upto) {
-                upto = gatherLaunch(done, n, arena);
-                gatherFinish(done, upto);
-            }
+            gatherAll(launched, n, arena);
+            gathered = true;
             if (gcDue) {                              // GC thread period (cpp:252-283)
-                e2sar_hip_reas_gc(reas, now, (uint64_t)flags.eventTimeout_ms, nullptr);
+                e2sar_hip_reas_gc(r, now, (uint64_t)flags.eventTimeout_ms, nullptr);
                 lastGc = now;
                 drainLost();
             }
             if (upkeepDue) upkeep(st);
         }
-        if (prof) pUpkeep += tick() - ta;
-        ta = tick();
+        clk.lap(pUpkeep);
         if (b) {
-            int rc = e2sar_hip_stream_wait_event(ctx, nullptr, d.h2dDone);
-            if (rc == 0) rc = e2sar_hip_reassemble_batch(reas, d.pkts, stride, d.lens, bn, bnow, nullptr);
+            int rc = e2sar_hip_stream_wait_event(c, nullptr, d.h2dDone.get());
+            if (rc == 0) rc = e2sar_hip_reassemble_batch(r, d.pkts.get(), stride, d.lens.get(), bn, bnow, nullptr);
             if (rc) lastErr = static_cast<E2SARErrorc>(-rc);
             else kernelInFlight = true;
             cur ^= 1;
         }
-        if (prof) pLaunch += tick() - ta;
-        ta = tick();
-        if (done < n) {                                // while that kernel runs
-            gatherFinish(done, upto);
-            for (done = upto; done < n; done = upto) {
-                upto = gatherLaunch(done, n, arena);
-                gatherFinish(done, upto);
-            }
-        }
-        if (prof) pGather += tick() - ta;
+        clk.lap(pLaunch);
+        if (!gathered) gatherAll(launched, n, arena);          // while that kernel runs
+        clk.lap(pGather);
     }
-    if (prof)
-        fprintf(stderr, "device thread: %.3f s, %llu cycles (%llu batches, %llu datagrams, %llu events), waiting %.3f s, "
-                        "poll %.3f s, upkeep/GC %.3f s, copy+launch %.3f s, gather %.3f s, last event at %.3f s\n",
-                (detail::now_us() - pT0) * 1e-6, (unsigned long long)pCycles, (unsigned long long)pBatches,
-                (unsigned long long)pDg, (unsigned long long)pEvents, pWait * 1e-6, pPoll * 1e-6, pUpkeep * 1e-6,
-                pLaunch * 1e-6, pGather * 1e-6, pLastEv * 1e-6);
+    clk.report("device thread: %.3f s, %llu cycles (%llu batches, %llu datagrams, %llu events), waiting %.3f s, "
+               "poll %.3f s, upkeep/GC %.3f s, copy+launch %.3f s, gather %.3f s, last event at %.3f s\n",
+               (unsigned long long)pCycles, (unsigned long long)pBatches, (unsigned long long)pDg,
+               (unsigned long long)pEvents, pWait * 1e-6, pPoll * 1e-6, pUpkeep * 1e-6, pLaunch * 1e-6, pGather * 1e-6,
+               pLastEv * 1e-6);
     uint32_t n = 0;
-    if (e2sar_hip_reas_poll(reas, recs.data(), (uint32_t)recs.size(), &n) == 0 && n) {
-        uint8_t *arena = e2sar_hip_reas_arena(reas);
-        for (uint32_t done = 0, upto; done < n; done = upto) {
-            upto = gatherLaunch(done, n, arena);
-            gatherFinish(done, upto);
-        }
-    }
+    if (e2sar_hip_reas_poll(r, recs.data(), (uint32_t)recs.size(), &n) == 0 && n) gatherAll(0, n, e2sar_hip_reas_arena(r));
     drainLost();
 }
 
@@ -628,45 +607,29 @@ result<int> Reassembler::openAndStart() noexcept
 {
     auto &m = *impl;
     if (m.started) return 0;
-    std::vector<std::vector<int>> tfds(m.numRecvThreads);
+    std::vector<std::vector<detail::Fd>> tfds(m.numRecvThreads);   // closed on every early return
     for (size_t t = 0; t < m.numRecvThreads; t++) {
         for (uint16_t port : m.threadsToPorts[t]) {
-            const int fd = socket(m.v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0);
-            if (fd < 0) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
-            setsockopt(fd, SOL_SOCKET, SO_RCVBUF, &m.flags.rcvSocketBufSize, sizeof(int));
+            const auto addr = detail::sock_addr(m.dataIP, port, m.v6);
+            if (!addr.ok) return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad data address " + m.dataIP};
+            detail::Fd fd(socket(m.v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0));
+            if (!fd.valid()) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
+            setsockopt(fd.get(), SOL_SOCKET, SO_RCVBUF, &m.flags.rcvSocketBufSize, sizeof(int));
             const int one = 1;
-            setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
-            sockaddr_storage ss{};
-            socklen_t sl;
-            if (m.v6) {
-                auto *a = reinterpret_cast<sockaddr_in6 *>(&ss);
-                a->sin6_family = AF_INET6;
-                a->sin6_port = htons(port);
-                inet_pton(AF_INET6, m.dataIP.c_str(), &a->sin6_addr);
-                sl = sizeof(sockaddr_in6);
-            } else {
-                auto *a = reinterpret_cast<sockaddr_in *>(&ss);
-                a->sin_family = AF_INET;
-                a->sin_port = htons(port);
-                inet_pton(AF_INET, m.dataIP.c_str(), &a->sin_addr);
-                sl = sizeof(sockaddr_in);
-            }
-            if (bind(fd, reinterpret_cast<sockaddr *>(&ss), sl) != 0) {
+            setsockopt(fd.get(), SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
+            if (bind(fd.get(), addr.sa(), addr.len) != 0) {
                 const std::string err = strerror(errno);
-                close(fd);
-                for (auto &v : tfds)
-                    for (int f : v) close(f);
                 return E2SARErrorInfo{E2SARErrorc::SocketError, "bind port " + std::to_string(port) + ": " + err};
             }
-            tfds[t].push_back(fd);
+            tfds[t].push_back(std::move(fd));
         }
     }
     m.stop = false;
     m.recvActive = (int)m.numRecvThreads;
     for (size_t t = 0; t < m.numRecvThreads; t++)
-        m.recvThreads.emplace_back([&m, t, fds = tfds[t]] {
-            m.recvBody(t, fds, m.threadsToPorts[t]);
-            for (int f : fds) close(f);
+        m.recvThreads.emplace_back([&m, t, fds = std::move(tfds[t])]() mutable {
+            m.recvBody(fds, m.threadsToPorts[t]);
+            fds.clear();                // the sockets close before the device thread hears of it
             m.recvActive--;
             m.bFullCv.notify_one();
         });
@@ -675,19 +638,24 @@ result<int> Reassembler::openAndStart() noexcept
     return 0;
 }
 
-// cpp:626-641
-result<int> Reassembler::getEvent(uint8_t **event, size_t *bytes, EventNum_t *eventNum, uint16_t *dataId) noexcept
+// the front of the event queue (eMu held), its buffer handed to the caller; -1 when empty
+int Reassembler::Impl::popEvent(uint8_t **event, size_t *bytes, EventNum_t *eventNum, uint16_t *dataId)
 {
-    auto &m = *impl;
-    std::lock_guard<std::mutex> lk(m.eMu);
-    if (m.evq.empty()) return -1;
-    const auto e = m.evq.front();
-    m.evq.pop_front();
-    *event = e.event;
+    if (evq.empty()) return -1;
+    Ev &e = evq.front();
+    *event = e.event.release();
     *bytes = e.bytes;
     *eventNum = e.eventNum;
     *dataId = e.dataId;
+    evq.pop_front();
     return 0;
+}
+
+// cpp:626-641
+result<int> Reassembler::getEvent(uint8_t **event, size_t *bytes, EventNum_t *eventNum, uint16_t *dataId) noexcept
+{
+    std::lock_guard<std::mutex> lk(impl->eMu);
+    return impl->popEvent(event, bytes, eventNum, dataId);
 }
 
 // cpp:643-676: wait in 10 ms slices; wait_ms == 0 waits until stopThreads()
@@ -703,26 +671,27 @@ result<int> Reassembler::recvEvent(uint8_t **event, size_t *bytes, EventNum_t *e
         if (wait_ms && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(wait_ms) && m.evq.empty())
             return -1;
     }
-    const auto e = m.evq.front();
-    m.evq.pop_front();
-    *event = e.event;
-    *bytes = e.bytes;
-    *eventNum = e.eventNum;
-    *dataId = e.dataId;
-    return 0;
+    return m.popEvent(event, bytes, eventNum, dataId);
+}
+
+// the device's counters: live once started, else (or on failure) the device thread's last copy
+e2sar_hip_reas_stats Reassembler::Impl::deviceStats()
+{
+    e2sar_hip_reas_stats st{};
+    if (!started || e2sar_hip_reas_get_stats(reas.get(), &st) != 0) {
+        std::lock_guard<std::mutex> lk(sMu);
+        st = lastStats;
+    }
+    return st;
 }
 
 const Reassembler::ReportedStats Reassembler::getStats() const noexcept
 {
     auto &m = *impl;
-    e2sar_hip_reas_stats st{};
-    if (!m.started || e2sar_hip_reas_get_stats(m.reas, &st) != 0) {
-        std::lock_guard<std::mutex> lk(m.sMu);
-        st = m.lastStats;
-    }
+    const e2sar_hip_reas_stats st = m.deviceStats();
     ReportedStats r{};
     r.enqueueLoss = st.enqueueLoss + m.hostEnqueueLoss.load();
-    r.reassemblyLoss = st.reassemblyLoss + m.hostReassemblyLoss.load();
+    r.reassemblyLoss = st.reassemblyLoss;
     r.eventSuccess = st.eventSuccess;
     r.lastErrno = m.lastErrno.load();
     r.grpcErrCnt = 0;
@@ -764,11 +733,7 @@ const std::string Reassembler::get_dataIP() const noexcept { return impl->dataIP
 const Reassembler::DeviceStats Reassembler::getDeviceStats() const noexcept
 {
     auto &m = *impl;
-    e2sar_hip_reas_stats st{};
-    if (!m.started || e2sar_hip_reas_get_stats(m.reas, &st) != 0) {
-        std::lock_guard<std::mutex> lk(m.sMu);
-        st = m.lastStats;
-    }
+    const e2sar_hip_reas_stats st = m.deviceStats();
     return DeviceStats{st.tableUsed, st.arenaUsed, m.upkeeps.load(), st.inProgress, st.errorFlags};
 }
 

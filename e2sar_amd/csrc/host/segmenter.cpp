@@ -7,10 +7,7 @@
 // batch comes back to pinned memory in one copy and leaves through sendmmsg, one call
 // per event on a round-robin socket (the reference's sendmmsg optimisation, :772-857).
 // sendEvent() is the synchronous single-event form (cpp:901-917).
-#include <arpa/inet.h>
-#include <netinet/in.h>
 #include <sys/socket.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -35,32 +32,33 @@ struct Segmenter::Impl {
     uint16_t dataId;
     uint32_t eventSrcId;
     SegmenterFlags flags;
-    std::vector<int> cores;
     bool useV6 = false;
     uint16_t mtu = 1500;
     std::string iface;               // outgoing interface of the data address (getIntf)
     size_t maxPld = 0;
     uint32_t stride = 0;
 
-    // device + staging
-    e2sar_hip_ctx *ctx = nullptr;
-    void *stream = nullptr;
-    uint8_t *dEvents = nullptr;
+    // device + staging.  Teardown is the reverse of this declaration order: ~Impl first
+    // synchronises the stream; then the buffers go, before the context that frees the device
+    // ones; the context is destroyed while its stream is alive (e2sar_hip_ctx_destroy
+    // synchronises it); the stream goes last.
+    detail::Stream stream;
+    detail::Ctx ctx;
+    detail::DeviceBuf<uint8_t> dEvents;
     size_t dEventsCap = 0;
-    e2sar_hip_seg_event *dDesc = nullptr;
+    detail::DeviceBuf<e2sar_hip_seg_event> dDesc;
     size_t dDescCap = 0;
-    uint8_t *dPkts = nullptr;
-    uint32_t *dLens = nullptr;
-    uint8_t *hPkts = nullptr;
-    uint32_t *hLens = nullptr;
+    detail::DeviceBuf<uint8_t> dPkts;
+    detail::DeviceBuf<uint32_t> dLens;
+    detail::Pinned<uint8_t> hPkts;
+    detail::Pinned<uint32_t> hLens;
     size_t pktCap = 0;
     std::vector<e2sar_hip_seg_event> hDesc;
     std::mutex devMu;
 
     // sockets
-    std::vector<int> fds;
-    std::vector<sockaddr_storage> dsts;
-    socklen_t dstLen = 0;
+    std::vector<detail::Fd> fds;
+    std::vector<detail::SockAddr> dsts;
     size_t rr = 0;
 
     // stats (e2sarDPSegmenter.hpp:149-161)
@@ -71,9 +69,8 @@ struct Segmenter::Impl {
 
     // Sync thread (useCP): a SyncHdr to the URI's sync address every syncPeriodMs
     // (e2sarDPSegmenter.cpp:242-373, fillSyncHdr hpp:583-591)
-    int syncFd = -1;
-    sockaddr_storage syncDst{};
-    socklen_t syncDstLen = 0;
+    detail::Fd syncFd;
+    detail::SockAddr syncDst;
     std::thread syncThread;
     std::mutex syncMu;
     std::condition_variable syncCv;
@@ -103,8 +100,8 @@ struct Segmenter::Impl {
     bool addEntropy = false;                              // clock LSBs need help (cpp:50)
     std::chrono::steady_clock::time_point paceNext{};   // rate pacing: earliest start of the next event
 
-    Impl(const EjfatURI &u, uint16_t did, uint32_t esid, std::vector<int> c, const SegmenterFlags &f)
-        : uri(u), dataId(did), eventSrcId(esid), flags(f), cores(std::move(c))
+    Impl(const EjfatURI &u, uint16_t did, uint32_t esid, const SegmenterFlags &f)
+        : uri(u), dataId(did), eventSrcId(esid), flags(f)
     {
     }
     ~Impl();
@@ -112,6 +109,9 @@ struct Segmenter::Impl {
     void sanity();
     result<int> ensure(size_t eventBytes, size_t nEvents, size_t nPackets);
     result<int> sendBatch(std::vector<Item> &items);
+    result<int> segmentBatch(const std::vector<Item> &items);
+    void pace(size_t eventBytes);
+    result<int> sendEvents(const std::vector<Item> &items);
     void threadBody();
     result<int> syncOpen();
     void syncSend();
@@ -122,18 +122,7 @@ struct Segmenter::Impl {
 Segmenter::Impl::~Impl()
 {
     syncHalt();
-    for (int fd : fds) close(fd);
-    if (ctx) {
-        e2sar_hip_stream_sync(ctx, stream);
-        if (dEvents) e2sar_hip_device_free(ctx, dEvents);
-        if (dDesc) e2sar_hip_device_free(ctx, dDesc);
-        if (dPkts) e2sar_hip_device_free(ctx, dPkts);
-        if (dLens) e2sar_hip_device_free(ctx, dLens);
-        if (hPkts) e2sar_hip_host_free(hPkts);
-        if (hLens) e2sar_hip_host_free(hLens);
-        e2sar_hip_ctx_destroy(ctx);
-    }
-    if (stream) e2sar_hip_stream_destroy(stream);
+    if (ctx) e2sar_hip_stream_sync(ctx.get(), stream.get());
 }
 
 namespace detail {
@@ -208,59 +197,50 @@ static void init_impl(Segmenter::Impl &m)
     m.maxPld = e2sar_hip_max_pld_len(m.mtu, m.useV6 ? 1 : 0);     // cpp:113
     m.addEntropy = !(detail::clock_entropy_bits() > kMinClockEntropy);   // cpp:50
     m.stride = e2sar_hip_packet_stride(m.maxPld);
-    int rc = e2sar_hip_stream_create(m.flags.gpuDevice, &m.stream);
-    if (rc == 0) rc = e2sar_hip_ctx_create(m.flags.gpuDevice, m.stream, &m.ctx);
+    int rc = detail::make(m.stream, e2sar_hip_stream_create, m.flags.gpuDevice);
+    if (rc == 0) rc = detail::make(m.ctx, e2sar_hip_ctx_create, m.flags.gpuDevice, m.stream.get());
     if (rc) throw E2SARException(std::string("Unable to open GPU ") + std::to_string(m.flags.gpuDevice) + ": " +
                                  e2sar_hip_last_error());
 }
 
 Segmenter::Segmenter(const EjfatURI &uri, uint16_t dataId, uint32_t eventSrcId, std::vector<int> cpuCoreList,
                      const SegmenterFlags &sflags)
-    : impl(new Impl(uri, dataId, eventSrcId, std::move(cpuCoreList), sflags))
-{
-    init_impl(*impl);
-}
+    : Segmenter(uri, dataId, eventSrcId, sflags) {}      // the core list is accepted and not used
 
 Segmenter::Segmenter(const EjfatURI &uri, uint16_t dataId, uint32_t eventSrcId, const SegmenterFlags &sflags)
-    : impl(new Impl(uri, dataId, eventSrcId, {}, sflags))
+    : impl(new Impl(uri, dataId, eventSrcId, sflags))
 {
     init_impl(*impl);
 }
 
 Segmenter::~Segmenter() { stopThreads(); }
 
+// Grow the staging for a batch.  A buffer that grows is released here, before the batch uses
+// the stream: the batch that used it last ended with a stream sync (segmentBatch).
 result<int> Segmenter::Impl::ensure(size_t eventBytes, size_t nEvents, size_t nPackets)
 {
+    using detail::alloc_device;
+    using detail::alloc_pinned;
     int rc;
     if (eventBytes > dEventsCap) {
-        if (dEvents) e2sar_hip_device_free(ctx, dEvents);
         dEventsCap = std::max(eventBytes, dEventsCap * 2);
-        if ((rc = e2sar_hip_device_alloc(ctx, dEventsCap, reinterpret_cast<void **>(&dEvents)))) {
+        if ((rc = alloc_device(ctx.get(), dEventsCap, dEvents))) {
             dEventsCap = 0;
             return hip_error(rc, "device event staging");
         }
     }
     if (nEvents > dDescCap) {
-        if (dDesc) e2sar_hip_device_free(ctx, dDesc);
         dDescCap = std::max<size_t>(nEvents, 64);
-        if ((rc = e2sar_hip_device_alloc(ctx, dDescCap * sizeof(e2sar_hip_seg_event),
-                                         reinterpret_cast<void **>(&dDesc)))) {
+        if ((rc = alloc_device(ctx.get(), dDescCap, dDesc))) {
             dDescCap = 0;
             return hip_error(rc, "device event table");
         }
     }
     if (nPackets > pktCap) {
-        if (dPkts) e2sar_hip_device_free(ctx, dPkts);
-        if (dLens) e2sar_hip_device_free(ctx, dLens);
-        if (hPkts) e2sar_hip_host_free(hPkts);
-        if (hLens) e2sar_hip_host_free(hLens);
-        dPkts = hPkts = nullptr;
-        dLens = hLens = nullptr;
+        dPkts.reset(), dLens.reset(), hPkts.reset(), hLens.reset();   // all four go before any comes back
         pktCap = std::max(nPackets, pktCap * 2);
-        if ((rc = e2sar_hip_device_alloc(ctx, pktCap * stride, reinterpret_cast<void **>(&dPkts))) ||
-            (rc = e2sar_hip_device_alloc(ctx, pktCap * 4, reinterpret_cast<void **>(&dLens))) ||
-            (rc = e2sar_hip_host_alloc(pktCap * stride, reinterpret_cast<void **>(&hPkts))) ||
-            (rc = e2sar_hip_host_alloc(pktCap * 4, reinterpret_cast<void **>(&hLens)))) {
+        if ((rc = alloc_device(ctx.get(), pktCap * stride, dPkts)) || (rc = alloc_device(ctx.get(), pktCap, dLens)) ||
+            (rc = alloc_pinned(pktCap * stride, hPkts)) || (rc = alloc_pinned(pktCap, hLens))) {
             pktCap = 0;
             return hip_error(rc, "datagram staging");
         }
@@ -272,6 +252,15 @@ result<int> Segmenter::Impl::ensure(size_t eventBytes, size_t nEvents, size_t nP
 result<int> Segmenter::Impl::sendBatch(std::vector<Item> &items)
 {
     std::lock_guard<std::mutex> lk(devMu);
+    auto r = segmentBatch(items);
+    if (r.has_error()) return r;
+    return sendEvents(items);
+}
+
+// Plan the batch, stage its events in HBM, launch seg_kernel and bring the datagrams back to
+// pinned memory; returns with the stream synchronised.
+result<int> Segmenter::Impl::segmentBatch(const std::vector<Item> &items)
+{
     hDesc.resize(items.size());
     size_t total = 0;
     for (size_t i = 0; i < items.size(); i++) {
@@ -291,10 +280,10 @@ result<int> Segmenter::Impl::sendBatch(std::vector<Item> &items)
     for (size_t i = 0; i < items.size(); i++) {
         const size_t off = reinterpret_cast<size_t>(hDesc[i].data);
         if (items[i].bytes &&
-            (rc = e2sar_hip_memcpy_async(ctx, dEvents + off, items[i].event, items[i].bytes, 0, nullptr)))
+            (rc = e2sar_hip_memcpy_async(ctx.get(), dEvents.get() + off, items[i].event, items[i].bytes, 0, nullptr)))
             return hip_error(rc, "event copy to device");
         auto &d = hDesc[i];
-        d.data = dEvents + off;
+        d.data = dEvents.get() + off;
         // lbEventNum = wall clock in microseconds, its low 8 bits random when the clock has
         // too little entropy there (cpp:707-719, addClockEntropy hpp:600-603); entropy 0 =>
         // random (cpp:727-728)
@@ -304,22 +293,57 @@ result<int> Segmenter::Impl::sendBatch(std::vector<Item> &items)
         d.entropy = items[i].entropy ? items[i].entropy : (uint16_t)(rng() & 0xFFFF);
         d.reserved = 0;
     }
-    if ((rc = e2sar_hip_memcpy_async(ctx, dDesc, hDesc.data(), items.size() * sizeof(e2sar_hip_seg_event), 0,
+    if ((rc = e2sar_hip_memcpy_async(ctx.get(), dDesc.get(), hDesc.data(), items.size() * sizeof(e2sar_hip_seg_event), 0,
                                      nullptr)))
         return hip_error(rc, "event table copy");
-    if ((rc = e2sar_hip_segment_batch(ctx, dDesc, (uint32_t)items.size(), maxPk, flags.lbHdrVersion,
-                                      (uint32_t)maxPld, 1, dPkts, stride, dLens, nullptr)))
+    if ((rc = e2sar_hip_segment_batch(ctx.get(), dDesc.get(), (uint32_t)items.size(), maxPk, flags.lbHdrVersion,
+                                      (uint32_t)maxPld, 1, dPkts.get(), stride, dLens.get(), nullptr)))
         return hip_error(rc, "segment_batch");
     // device -> host by the GPU's own stores into pinned memory (one copy_spans launch), not
     // by DMA: host->device copies (this Segmenter's events, a Reassembler's datagrams in the
     // same process) keep the DMA engines, which serialise when both directions share them
     // (tools/bench_hostpath.py: both directions at once 13.5 GiB/s each with DMA both ways,
     // 21.0 with device->host by kernel stores)
-    const e2sar_hip_copy_span back[2] = {{dPkts, hPkts, (uint64_t)nPk * stride}, {dLens, hLens, (uint64_t)nPk * 4}};
-    if ((rc = e2sar_hip_copy_spans(ctx, back, 2, nullptr)) || (rc = e2sar_hip_stream_sync(ctx, nullptr)))
+    const e2sar_hip_copy_span back[2] = {{dPkts.get(), hPkts.get(), (uint64_t)nPk * stride},
+                                         {dLens.get(), hLens.get(), (uint64_t)nPk * 4}};
+    if ((rc = e2sar_hip_copy_spans(ctx.get(), back, 2, nullptr)) || (rc = e2sar_hip_stream_sync(ctx.get(), nullptr)))
         return hip_error(rc, "datagram copy to host");
+    return 0;
+}
 
-    // one sendmmsg per event, round-robin over the sockets (cpp:404, 834-857)
+// start-to-start pacing, as the reference's busy wait from the dispatch time (cpp:401,
+// 447-450): the next event may start interval after this one started
+void Segmenter::Impl::pace(size_t eventBytes)
+{
+    if (!(flags.rateGbps > 0)) return;
+    const auto now = std::chrono::steady_clock::now();
+    if (paceNext > now) {
+        if (paceNext - now > std::chrono::microseconds(200))
+            std::this_thread::sleep_until(paceNext - std::chrono::microseconds(100));
+        while (std::chrono::steady_clock::now() < paceNext) {
+        }
+    } else {
+        paceNext = now;   // behind schedule: no credit is banked
+    }
+    paceNext += std::chrono::nanoseconds((int64_t)((double)eventBytes * 8.0 / flags.rateGbps));
+}
+
+// at most this many datagrams per sendmmsg call: the kernel hands a loopback or local
+// receiver's datagrams over when the call returns, and a whole event's worth in one call
+// (731 at MTU 1500) overruns its per-CPU backlog; short calls keep the sender at the rate
+// the receiving side drains.  E2SAR_SEND_CHUNK, default 64, 0 = unlimited.
+static uint32_t send_chunk()
+{
+    static const char *const v = getenv("E2SAR_SEND_CHUNK");
+    const unsigned long x = v ? strtoul(v, nullptr, 10) : 64ul;
+    return (uint32_t)(x ? x : 0xFFFFFFFFul);
+}
+
+// one sendmmsg per event, round-robin over the sockets (cpp:404, 834-857), out of the pinned
+// datagram batch segmentBatch left
+result<int> Segmenter::Impl::sendEvents(const std::vector<Item> &items)
+{
+    const uint32_t sendChunk = send_chunk();
     std::vector<mmsghdr> mv;
     std::vector<iovec> iv;
     for (size_t i = 0; i < items.size(); i++) {
@@ -329,41 +353,19 @@ result<int> Segmenter::Impl::sendBatch(std::vector<Item> &items)
         mv.assign(n, mmsghdr{});
         iv.resize(n);
         for (uint32_t k = 0; k < n; k++) {
-            iv[k].iov_base = hPkts + (size_t)(base + k) * stride;
+            iv[k].iov_base = hPkts.get() + (size_t)(base + k) * stride;
             iv[k].iov_len = hLens[base + k];
             mv[k].msg_hdr.msg_iov = &iv[k];
             mv[k].msg_hdr.msg_iovlen = 1;
             if (!flags.connectedSocket) {
-                mv[k].msg_hdr.msg_name = &dsts[s];
-                mv[k].msg_hdr.msg_namelen = dstLen;
+                mv[k].msg_hdr.msg_name = &dsts[s].ss;
+                mv[k].msg_hdr.msg_namelen = dsts[s].len;
             }
         }
-        // start-to-start pacing, as the reference's busy wait from the dispatch time
-        // (cpp:401, 447-450): the next event may start interval after this one started
-        if (flags.rateGbps > 0) {
-            const auto now = std::chrono::steady_clock::now();
-            if (paceNext > now) {
-                if (paceNext - now > std::chrono::microseconds(200))
-                    std::this_thread::sleep_until(paceNext - std::chrono::microseconds(100));
-                while (std::chrono::steady_clock::now() < paceNext) {
-                }
-            } else {
-                paceNext = now;   // behind schedule: no credit is banked
-            }
-            paceNext += std::chrono::nanoseconds((int64_t)((double)items[i].bytes * 8.0 / flags.rateGbps));
-        }
-        // at most sendChunk datagrams per call: the kernel hands a loopback or local
-        // receiver's datagrams over when the call returns, and a whole event's worth in one
-        // call (731 at MTU 1500) overruns its per-CPU backlog; short calls keep the sender
-        // at the rate the receiving side drains
-        static const uint32_t sendChunk = [] {
-            const char *v = getenv("E2SAR_SEND_CHUNK");
-            const unsigned long x = v ? strtoul(v, nullptr, 10) : 64ul;
-            return (uint32_t)(x ? x : 0xFFFFFFFFul);
-        }();
+        pace(items[i].bytes);
         uint32_t sent = 0;
         while (sent < n) {
-            const int r = sendmmsg(fds[s], mv.data() + sent, std::min(n - sent, sendChunk), 0);
+            const int r = sendmmsg(fds[s].get(), mv.data() + sent, std::min(n - sent, sendChunk), 0);
             if (r < 0) {
                 if (errno == EINTR) continue;
                 if (errno == EAGAIN || errno == ENOBUFS) {
@@ -423,29 +425,13 @@ result<int> Segmenter::Impl::syncOpen()
     if (sa.has_error()) return sa.error();
     const std::string &host = sa.value().first;
     const bool v6 = host.find(':') != std::string::npos;
-    syncDst = sockaddr_storage{};
-    int ok;
-    if (v6) {
-        auto *a = reinterpret_cast<sockaddr_in6 *>(&syncDst);
-        a->sin6_family = AF_INET6;
-        a->sin6_port = htons(sa.value().second);
-        ok = inet_pton(AF_INET6, host.c_str(), &a->sin6_addr);
-        syncDstLen = sizeof(sockaddr_in6);
-    } else {
-        auto *a = reinterpret_cast<sockaddr_in *>(&syncDst);
-        a->sin_family = AF_INET;
-        a->sin_port = htons(sa.value().second);
-        ok = inet_pton(AF_INET, host.c_str(), &a->sin_addr);
-        syncDstLen = sizeof(sockaddr_in);
-    }
-    if (ok != 1) return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad sync address " + host};
-    syncFd = socket(v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0);
-    if (syncFd < 0 ||
-        (flags.connectedSocket && connect(syncFd, reinterpret_cast<sockaddr *>(&syncDst), syncDstLen) != 0)) {
+    syncDst = detail::sock_addr(host, sa.value().second, v6);
+    if (!syncDst.ok) return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad sync address " + host};
+    syncFd.reset(socket(v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0));
+    if (!syncFd.valid() || (flags.connectedSocket && connect(syncFd.get(), syncDst.sa(), syncDst.len) != 0)) {
         syncErrCnt++;
         syncLastErrno = errno;
-        if (syncFd >= 0) close(syncFd);
-        syncFd = -1;
+        syncFd.reset();
         return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(syncLastErrno.load())};
     }
     return 0;
@@ -463,8 +449,8 @@ void Segmenter::Impl::syncSend()
     hdr.set(eventSrcId, detail::now_us(), 1000000u, nowNs);
     syncMsgCnt++;
     const ssize_t r = flags.connectedSocket
-                          ? send(syncFd, &hdr, sizeof(hdr), 0)
-                          : sendto(syncFd, &hdr, sizeof(hdr), 0, reinterpret_cast<sockaddr *>(&syncDst), syncDstLen);
+                          ? send(syncFd.get(), &hdr, sizeof(hdr), 0)
+                          : sendto(syncFd.get(), &hdr, sizeof(hdr), 0, syncDst.sa(), syncDst.len);
     if (r < 0) {
         syncErrCnt++;
         syncLastErrno = errno;
@@ -493,8 +479,7 @@ void Segmenter::Impl::syncHalt()
     }
     syncCv.notify_all();
     if (syncThread.joinable()) syncThread.join();
-    if (syncFd >= 0) close(syncFd);     // _close (cpp:279, 339-343)
-    syncFd = -1;
+    syncFd.reset();                     // _close (cpp:279, 339-343)
 }
 
 // cpp:160-191 (the Sync thread and its warm-up first, as there); sockets as in cpp:470-657
@@ -515,50 +500,22 @@ result<int> Segmenter::openAndStart() noexcept
     }
     std::uniform_int_distribution<int> portDist(10000, 65535);
     for (size_t i = 0; i < m.flags.numSendSockets; i++) {
-        sockaddr_storage ss{};
-        socklen_t sl;
         const uint16_t port = (uint16_t)(addr.value().second + (m.flags.multiPort ? i : 0));
-        if (m.useV6) {
-            auto *a = reinterpret_cast<sockaddr_in6 *>(&ss);
-            a->sin6_family = AF_INET6;
-            a->sin6_port = htons(port);
-            if (inet_pton(AF_INET6, addr.value().first.c_str(), &a->sin6_addr) != 1)
-                return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad IPv6 data address"};
-            sl = sizeof(sockaddr_in6);
-        } else {
-            auto *a = reinterpret_cast<sockaddr_in *>(&ss);
-            a->sin_family = AF_INET;
-            a->sin_port = htons(port);
-            if (inet_pton(AF_INET, addr.value().first.c_str(), &a->sin_addr) != 1)
-                return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad IPv4 data address"};
-            sl = sizeof(sockaddr_in);
-        }
-        const int fd = socket(m.useV6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0);
-        if (fd < 0) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
-        setsockopt(fd, SOL_SOCKET, SO_SNDBUF, &m.flags.sndSocketBufSize, sizeof(int));
+        const auto dst = detail::sock_addr(addr.value().first, port, m.useV6);
+        if (!dst.ok)
+            return E2SARErrorInfo{E2SARErrorc::ParameterError, m.useV6 ? "bad IPv6 data address" : "bad IPv4 data address"};
+        detail::Fd fd(socket(m.useV6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0));
+        if (!fd.valid()) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
+        setsockopt(fd.get(), SOL_SOCKET, SO_SNDBUF, &m.flags.sndSocketBufSize, sizeof(int));
         // random source port (hpp:237); fall back to an ephemeral one if taken
         for (int tries = 0; tries < 16; tries++) {
-            sockaddr_storage src{};
-            if (m.useV6) {
-                auto *a = reinterpret_cast<sockaddr_in6 *>(&src);
-                a->sin6_family = AF_INET6;
-                a->sin6_port = htons((uint16_t)portDist(m.rng));
-                a->sin6_addr = in6addr_any;
-            } else {
-                auto *a = reinterpret_cast<sockaddr_in *>(&src);
-                a->sin_family = AF_INET;
-                a->sin_port = htons((uint16_t)portDist(m.rng));
-                a->sin_addr.s_addr = htonl(INADDR_ANY);
-            }
-            if (bind(fd, reinterpret_cast<sockaddr *>(&src), sl) == 0) break;
+            const auto src = detail::sock_addr("", (uint16_t)portDist(m.rng), m.useV6);
+            if (bind(fd.get(), src.sa(), src.len) == 0) break;
         }
-        if (m.flags.connectedSocket && connect(fd, reinterpret_cast<sockaddr *>(&ss), sl) != 0) {
-            close(fd);
+        if (m.flags.connectedSocket && connect(fd.get(), dst.sa(), dst.len) != 0)
             return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
-        }
-        m.fds.push_back(fd);
-        m.dsts.push_back(ss);
-        m.dstLen = sl;
+        m.fds.push_back(std::move(fd));
+        m.dsts.push_back(dst);
     }
     m.stop = false;
     m.sendThread = std::thread([&m] { m.threadBody(); });

@@ -16,7 +16,6 @@
 #include <cerrno>
 #include <cstdlib>
 #include <cstring>
-#include <unistd.h>
 #include <fstream>
 #include <map>
 #include <sstream>
@@ -179,6 +178,27 @@ double ini_num(const std::map<std::string, std::string> &m, const std::string &k
     return std::atof(it->second.c_str());
 }
 
+SockAddr sock_addr(const std::string &host, uint16_t port, bool v6)
+{
+    SockAddr r;
+    int ok = 1;                        // an empty host keeps the zeroed address: the wildcard
+    if (v6) {
+        auto *a = reinterpret_cast<sockaddr_in6 *>(&r.ss);
+        a->sin6_family = AF_INET6;
+        a->sin6_port = htons(port);
+        if (!host.empty()) ok = inet_pton(AF_INET6, host.c_str(), &a->sin6_addr);
+        r.len = sizeof(sockaddr_in6);
+    } else {
+        auto *a = reinterpret_cast<sockaddr_in *>(&r.ss);
+        a->sin_family = AF_INET;
+        a->sin_port = htons(port);
+        if (!host.empty()) ok = inet_pton(AF_INET, host.c_str(), &a->sin_addr);
+        r.len = sizeof(sockaddr_in);
+    }
+    r.ok = ok == 1;
+    return r;
+}
+
 }  // namespace detail
 
 // e2sarDPSegmenter.cpp:950-996 (warmUpMS read as a number here; the reference reads it as bool)
@@ -241,10 +261,6 @@ result<ReassemblerFlagsT> ReassemblerFlagsT::getFromINI(const std::string &iniFi
     return f;
 }
 
-}  // namespace e2sar
-
-namespace e2sar {
-
 result<EjfatURI> EjfatURI::getFromString(const std::string &uri, TokenType tt, bool preferV6) noexcept
 {
     try {
@@ -274,37 +290,17 @@ result<std::string> getHostName() noexcept
 result<std::tuple<std::string, uint16_t>> getInterfaceAndMTU(const std::string &ip) noexcept
 {
     const bool v6 = ip.find(':') != std::string::npos;
-    sockaddr_storage ss{};
-    socklen_t sl;
-    if (v6) {
-        auto *a = reinterpret_cast<sockaddr_in6 *>(&ss);
-        a->sin6_family = AF_INET6;
-        a->sin6_port = htons(9);
-        if (inet_pton(AF_INET6, ip.c_str(), &a->sin6_addr) != 1) return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad IPv6 address " + ip};
-        sl = sizeof(sockaddr_in6);
-    } else {
-        auto *a = reinterpret_cast<sockaddr_in *>(&ss);
-        a->sin_family = AF_INET;
-        a->sin_port = htons(9);
-        if (inet_pton(AF_INET, ip.c_str(), &a->sin_addr) != 1) return E2SARErrorInfo{E2SARErrorc::ParameterError, "bad IPv4 address " + ip};
-        sl = sizeof(sockaddr_in);
-    }
-    const int fd = socket(v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0);
-    if (fd < 0) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
+    const auto dst = detail::sock_addr(ip, 9, v6);
+    if (!dst.ok) return E2SARErrorInfo{E2SARErrorc::ParameterError, std::string(v6 ? "bad IPv6 address " : "bad IPv4 address ") + ip};
+    const detail::Fd fd(socket(v6 ? AF_INET6 : AF_INET, SOCK_DGRAM, 0));
+    if (!fd.valid()) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
     // connect() on a UDP socket sends nothing; it makes the kernel pick the route
     sockaddr_storage local{};
     socklen_t ll = sizeof(local);
-    if (connect(fd, reinterpret_cast<sockaddr *>(&ss), sl) != 0 ||
-        getsockname(fd, reinterpret_cast<sockaddr *>(&local), &ll) != 0) {
-        const std::string err = strerror(errno);
-        close(fd);
-        return E2SARErrorInfo{E2SARErrorc::SocketError, "no route to " + ip + ": " + err};
-    }
+    if (connect(fd.get(), dst.sa(), dst.len) != 0 || getsockname(fd.get(), reinterpret_cast<sockaddr *>(&local), &ll) != 0)
+        return E2SARErrorInfo{E2SARErrorc::SocketError, "no route to " + ip + ": " + strerror(errno)};
     ifaddrs *ifa = nullptr;
-    if (getifaddrs(&ifa) != 0) {
-        close(fd);
-        return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
-    }
+    if (getifaddrs(&ifa) != 0) return E2SARErrorInfo{E2SARErrorc::SocketError, strerror(errno)};
     std::string name;
     for (ifaddrs *i = ifa; i && name.empty(); i = i->ifa_next) {
         if (!i->ifa_addr || i->ifa_addr->sa_family != local.ss_family) continue;
@@ -318,15 +314,10 @@ result<std::tuple<std::string, uint16_t>> getInterfaceAndMTU(const std::string &
         }
     }
     freeifaddrs(ifa);
-    if (name.empty()) {
-        close(fd);
-        return E2SARErrorInfo{E2SARErrorc::NotFound, "no interface holds the local address routed to " + ip};
-    }
+    if (name.empty()) return E2SARErrorInfo{E2SARErrorc::NotFound, "no interface holds the local address routed to " + ip};
     ifreq ifr{};
     strncpy(ifr.ifr_name, name.c_str(), IFNAMSIZ - 1);
-    const int rc = ioctl(fd, SIOCGIFMTU, &ifr);
-    close(fd);
-    if (rc != 0) return E2SARErrorInfo{E2SARErrorc::SocketError, std::string("SIOCGIFMTU: ") + strerror(errno)};
+    if (ioctl(fd.get(), SIOCGIFMTU, &ifr) != 0) return E2SARErrorInfo{E2SARErrorc::SocketError, std::string("SIOCGIFMTU: ") + strerror(errno)};
     // the MTU travels as u_int16_t, as in the reference (e2sarNetUtil.cpp:147-149 narrows
     // getMTU's size_t): loopback's 65536 reads as 0 there ("lo doesn't" report one,
     // e2sarDPSegmenter.cpp:86-88), and so it does here

@@ -672,3 +672,47 @@ def test_send_queue_full_consumes_an_event_number(E):
         evs[ev] = d[36:]
     assert sorted(evs) == list(range(cap)) + [cap + 1]        # number `cap` was consumed
     assert evs[cap + 1] == bufs[cap + 1] and evs[0] == bufs[0] and evs[cap - 1] == bufs[cap - 1]
+
+
+# ------------------------------- openAndStart failures ----------------------------
+
+def _reas_on(E, ip, port, port_range=-1):
+    uri = E.EjfatURI(f"ejfat://useless@192.168.100.1:9875/lb/1?sync=192.168.0.1:12345&data={DP}",
+                     E.EjfatURI.TokenType.instance)
+    f = E.DataPlane.Reassembler.ReassemblerFlags()
+    f.useCP = False
+    f.withLBHeader = True
+    f.portRange = port_range
+    f.arenaBytes = 16 << 20
+    return E.DataPlane.Reassembler(uri, E.IPAddress.from_string(ip), port, 1, f)
+
+
+def test_reassembler_rejects_a_malformed_data_ip(E):
+    # text inet_pton rejects must not bind the wildcard address: the reference throws on it
+    # (boost::asio::ip::make_address); here OpenAndStart reports it and nothing is started
+    reas = _reas_on(E, "300.1.1.1", next_port())
+    r = reas.OpenAndStart()
+    assert r.has_error()
+    assert r.error().code == E.E2SARErrorc.ParameterError, r.error()
+    assert "300.1.1.1" in r.error().message
+    del reas                                   # destroyed without hanging
+
+
+def test_failed_open_leaves_no_descriptors(E):
+    # the second port of a two-port range is taken (no SO_REUSEADDR on the holder): the bind
+    # fails after the first socket was opened, and every socket opened so far is closed once
+    port = next_port(2)
+    holder = socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
+    holder.bind((DP, port + 1))
+    try:
+        reas = _reas_on(E, DP, port, port_range=1)
+        assert reas.get_recvPorts() == (port, port + 1)
+        before = len(os.listdir("/proc/self/fd"))
+        r = reas.OpenAndStart()
+        assert r.has_error()
+        assert r.error().code == E.E2SARErrorc.SocketError, r.error()
+        assert str(port + 1) in r.error().message
+        del reas
+        assert len(os.listdir("/proc/self/fd")) == before
+    finally:
+        holder.close()
