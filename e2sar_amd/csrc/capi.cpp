@@ -18,10 +18,12 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <set>
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "e2sar_hip.h"
@@ -42,6 +44,15 @@ int fail(int code, const std::string &msg)
 int hip_fail(hipError_t e, const char *what)
 {
     return fail(E2SAR_HIP_ERR_SYSTEM, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// A device allocation the runtime refused, as "<what>: <error>".  The runtime also keeps the
+// error as the thread's last one, where the hipGetLastError of the next launcher (or of any
+// other user of the runtime in this process) would find it: reported here, so cleared here.
+int alloc_fail(hipError_t e, const char *what)
+{
+    (void)hipGetLastError();
+    return fail(E2SAR_HIP_ERR_MEMORY, std::string(what) + ": " + hipGetErrorString(e));
 }
 
 #define HIP_TRY(expr)                                   \
@@ -65,43 +76,95 @@ static void ctx_release(e2sar_hip_ctx *c)
     if (c && c->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete c;
 }
 
+/* ---------------- owners ---------------- */
+
+// What this file allocates is held by a move-only owner: outside the public free / destroy
+// entry points, these deleters are the only hipFree, hipEventDestroy and reference drop.
+namespace {
+
+template <auto Destroy> struct Deleter {
+    template <class T> void operator()(T *p) const { (void)Destroy(p); }
+};
+using DevMem = std::unique_ptr<void, Deleter<hipFree>>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Deleter<hipEventDestroy>>;
+using CtxRef = std::unique_ptr<e2sar_hip_ctx, Deleter<ctx_release>>;     // adopts a reference already taken
+static_assert(!std::is_copy_constructible_v<DevMem> && !std::is_copy_constructible_v<Event> &&
+                  !std::is_copy_constructible_v<CtxRef>,
+              "owners move, they do not copy");
+
+// hipMalloc into an owner; a failure leaves it empty
+hipError_t dev_alloc(DevMem &m, size_t bytes)
+{
+    void *p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    m.reset(e == hipSuccess ? p : nullptr);
+    return e;
+}
+
+// An internal buffer that grows (grow()): the allocation and its size
+struct GrowBuf {
+    DevMem mem;
+    size_t bytes = 0;
+};
+
+}  // namespace
+
+// The order in which a reassembler's memory goes is the reverse of the declarations below:
+// the destructor waits for the device, then the event, the retired buffers, the per-stream
+// scratch, both arenas, the alternate table and the state block are released, and the
+// reference on the context last.
 struct e2sar_hip_reas {
-    e2sar_hip_ctx *ctx = nullptr;
+    CtxRef ctx;                      // first, so destroyed last: the destructor sets its device
     e2sar_hip_reas_config cfg{};
+    // views into the memory below; compaction swaps the slots and arena of the two
     ReasDev dev{};
     ReasDev alt{};                   // second slots + arena (COMPACTABLE), same ctl/lists
-    void *stateMem = nullptr;        // slots | ctl | shards | occupancy shards | completed | lost
-    void *altSlots = nullptr;
+    DevMem state;                    // slots | ctl | shards | occupancy shards | completed | lost
+    DevMem altSlots;
+    DevMem arena[2];                 // owned by identity, whichever of dev / alt points at which
     // Internal buffers, one set PER STREAM (two batches launched on different streams must
     // not share work records or ready counters while both run): the reference-order sort
     // keys / records / sort storage, the PktInfo/FinishRec work buffer of reassemble_batch
     // (reference order, or batches above kFusedMaxBytes), the chained form's ready counters.
     // They grow on demand, never inside a graph capture, and a buffer they outgrow is kept
-    // (retired) until the reassembler is destroyed: a graph captured before the growth still
-    // holds its address.
+    // (retired) while a graph captured before the growth may still hold its address.
     struct Scratch {
-        void *roScratch = nullptr;
-        size_t roScratchBytes = 0;
+        GrowBuf ro;
         // a reference-order launch sequence failed part way: the key pass may have left run
         // counts that only the place / walk kernels reset, so the next batch re-zeroes them
         bool roDirty = false;
-        void *roWork = nullptr;
-        size_t roWorkBytes = 0;
-        void *tiles = nullptr;
-        size_t tilesBytes = 0;
+        GrowBuf work;
+        GrowBuf tiles;
     };
     std::map<hipStream_t, Scratch> scratch;
-    std::vector<void *> retired;
+    std::vector<DevMem> retired;
     // the streams launched on outside capture: poll / lost_poll / get_stats wait for those
     // streams only, not for the whole device (an event recorded on each at snapshot time --
     // not after every launch: a marker between kernels lengthens the next kernel's start)
     std::set<hipStream_t> streams;
-    hipEvent_t waitEv = nullptr;
+    Event waitEv;
     bool sawCapture = false;         // a launch was captured into a graph: snapshots wait for the device
     std::mutex mu;
+
+    e2sar_hip_reas(e2sar_hip_ctx *c, const e2sar_hip_reas_config &config) : ctx(c), cfg(config)
+    {
+        c->refs.fetch_add(1, std::memory_order_relaxed);
+    }
+    ~e2sar_hip_reas()
+    {
+        (void)hipSetDevice(ctx->device);
+        // launches on any stream (the caller's, a graph replay's) may still use the table, the
+        // arena and the internal buffers: wait for the device before the members free them
+        (void)hipDeviceSynchronize();
+    }
 };
 
 static bool ref_order(const e2sar_hip_reas *r) { return (r->cfg.flags & E2SAR_HIP_REAS_REFERENCE_ORDER) != 0; }
+
+static hipStream_t stream_of(const e2sar_hip_ctx *ctx, void *stream)
+{
+    return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+}
 
 static bool capturing(hipStream_t s)
 {
@@ -111,44 +174,62 @@ static bool capturing(hipStream_t s)
 
 // After a launch through this reassembler on stream s (caller holds r->mu): remember the
 // stream, so a later snapshot waits for exactly the streams this reassembler used.
-static hipError_t note_launch(e2sar_hip_reas *r, hipStream_t s)
+static void note_launch(e2sar_hip_reas *r, hipStream_t s)
 {
     if (capturing(s)) r->sawCapture = true;          // replays run wherever the caller puts them
     else r->streams.insert(s);
-    return hipSuccess;
+}
+
+// The prologue and epilogue of a call on a context: ctx must not be NULL; on its device and
+// (stream == NULL) its default stream run body(s).  body returns the call's hipError_t,
+// reported as "<what>: <error>", or, where it can fail in other ways or words, an ABI code
+// with the message already set.  An entry point with argument checks says "ctx is NULL"
+// itself before them: the device is set last.
+template <typename Body>
+static int ctx_call(const e2sar_hip_ctx *ctx, void *stream, const char *what, Body body)
+{
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream_of(ctx, stream);
+    if constexpr (std::is_same_v<decltype(body(s)), hipError_t>) {
+        const hipError_t e = body(s);
+        return e == hipSuccess ? E2SAR_HIP_OK : hip_fail(e, what);
+    } else {
+        return body(s);
+    }
 }
 
 // The prologue and epilogue of every launch through a reassembler: r must not be NULL; under
-// r->mu, on the device and (stream == NULL) the default stream of r's context -- or of `on`,
-// where the caller names another context -- run body(s), then remember the stream
-// (note_launch).  body returns the launch's hipError_t, reported as "<what>: <error>", or,
-// where it can fail in other ways or words, an ABI code with the message already set.
+// r->mu, a ctx_call on r's context -- or on `on`, where the caller names another context --
+// that runs body(s), then remembers the stream (note_launch).
 template <typename Body>
 static int reas_launch(e2sar_hip_reas *r, void *stream, const char *what, Body body, const e2sar_hip_ctx *on = nullptr)
 {
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     std::lock_guard<std::mutex> lk(r->mu);
-    if (!on) on = r->ctx;
-    HIP_TRY(hipSetDevice(on->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : on->stream;
-    hipError_t e = hipSuccess;
-    if constexpr (std::is_same_v<decltype(body(s)), hipError_t>) e = body(s);
-    else if (int rc = body(s)) return rc;
-    if (e == hipSuccess) e = note_launch(r, s);
-    if (e != hipSuccess) return hip_fail(e, what);
-    return E2SAR_HIP_OK;
+    if (!on) on = r->ctx.get();
+    const int rc = ctx_call(on, stream, what, body);
+    if (rc == E2SAR_HIP_OK) note_launch(r, stream_of(on, stream));
+    return rc;
 }
 
 /* ---------------- argument checks shared by the entry points ---------------- */
+
+// nPackets datagram slots at d_packets, whatever reads them: alignment, and 16-byte words a
+// 32-bit index can count
+static int check_packets(const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
+{
+    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
+    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
+    return E2SAR_HIP_OK;
+}
 
 // A batch of nPackets datagram slots of `stride` bytes at d_packets, for reassembler r.
 static int check_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
 {
     const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
     if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
-    if (((uintptr_t)d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
-    if ((uint64_t)nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
-    return E2SAR_HIP_OK;
+    return check_packets(d_packets, stride, nPackets);
 }
 
 // The caller's work buffer of a classified batch of n datagrams; tooSmall is the entry
@@ -178,6 +259,15 @@ static int check_world(uint32_t world, uint32_t self)
     return E2SAR_HIP_OK;
 }
 
+// What every routing form checks first, in this order: the context, the ranks, the slot stride.
+static int check_route(const e2sar_hip_ctx *ctx, uint32_t world, uint32_t self, uint32_t stride)
+{
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (int rc = check_world(world, self)) return rc;
+    if ((stride & 15u) || stride < 48u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16, >= 48");
+    return E2SAR_HIP_OK;
+}
+
 // reassemble_batch keeps the fused kernel up to this many bytes of datagram slots (a batch
 // that can still sit in the 256 MiB Infinity Cache) and switches to the split form above
 static constexpr uint64_t kFusedMaxBytes = 320ull << 20;
@@ -194,37 +284,22 @@ static bool cold_loads(const e2sar_hip_reas *r, uint32_t n, uint32_t stride)
 // batches may still read it, and a graph captured earlier holds its address.  Inside a
 // capture a buffer cannot grow (allocation there would break the capture): the call fails
 // with a LogicError naming the remedy instead.
-static int grow(e2sar_hip_reas *r, hipStream_t s, void *&buf, size_t &have, size_t need, bool *grew = nullptr)
+static int grow(e2sar_hip_reas *r, hipStream_t s, GrowBuf &b, size_t need, bool *grew = nullptr)
 {
     if (grew) *grew = false;
-    if (need <= have) return E2SAR_HIP_OK;
+    if (need <= b.bytes) return E2SAR_HIP_OK;
     if (capturing(s))
         return fail(E2SAR_HIP_ERR_LOGIC, "an internal buffer must grow for this batch size inside a graph capture: "
                                          "run one batch of the largest size on this stream before capturing");
     const size_t want = need + need / 4;
-    void *nb = nullptr;
-    hipError_t e = hipMalloc(&nb, want);
-    if (e != hipSuccess) return fail(E2SAR_HIP_ERR_MEMORY, std::string("hipMalloc(internal buffer): ") + hipGetErrorString(e));
-    if (buf) r->retired.push_back(buf);
-    buf = nb;
-    have = want;
+    DevMem nb;
+    const hipError_t e = dev_alloc(nb, want);
+    if (e != hipSuccess) return alloc_fail(e, "hipMalloc(internal buffer)");
+    if (b.mem) r->retired.push_back(std::move(b.mem));
+    b.mem = std::move(nb);
+    b.bytes = want;
     if (grew) *grew = true;
     return E2SAR_HIP_OK;
-}
-
-static void free_internal(e2sar_hip_reas *r)
-{
-    for (auto &kv : r->scratch) {
-        if (kv.second.roScratch) (void)hipFree(kv.second.roScratch);
-        if (kv.second.roWork) (void)hipFree(kv.second.roWork);
-        if (kv.second.tiles) (void)hipFree(kv.second.tiles);
-    }
-    r->scratch.clear();
-    for (void *p : r->retired) (void)hipFree(p);
-    r->retired.clear();
-    if (r->waitEv) (void)hipEventDestroy(r->waitEv);
-    r->waitEv = nullptr;
-    r->streams.clear();
 }
 
 // Free the internal buffers of stream s (caller holds r->mu and knows none of its launches
@@ -233,23 +308,10 @@ static void drop_scratch(e2sar_hip_reas *r, hipStream_t s)
 {
     auto it = r->scratch.find(s);
     if (it == r->scratch.end()) return;
-    for (void *p : {it->second.roScratch, it->second.roWork, it->second.tiles}) {
-        if (!p) continue;
-        if (r->sawCapture) r->retired.push_back(p);
-        else (void)hipFree(p);
-    }
+    if (r->sawCapture)
+        for (GrowBuf *b : {&it->second.ro, &it->second.work, &it->second.tiles})
+            if (b->mem) r->retired.push_back(std::move(b->mem));
     r->scratch.erase(it);
-}
-
-// Free whatever a partly built reassembler holds (every pointer starts null).
-static void reas_release(e2sar_hip_reas *r)
-{
-    free_internal(r);
-    if (r->altSlots) (void)hipFree(r->altSlots);
-    if (r->alt.arena && r->alt.arena != r->dev.arena) (void)hipFree(r->alt.arena);
-    if (r->dev.arena) (void)hipFree(r->dev.arena);
-    if (r->stateMem) (void)hipFree(r->stateMem);
-    delete r;
 }
 
 extern "C" {
@@ -302,32 +364,21 @@ int e2sar_hip_ctx_device(e2sar_hip_ctx *ctx) { return ctx ? ctx->device : -1; }
 
 int e2sar_hip_ctx_sync(e2sar_hip_ctx *ctx)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, nullptr, "hipStreamSynchronize(ctx->stream)", [](hipStream_t s) { return hipStreamSynchronize(s); });
 }
-
-// Large device buffers (arena, e2sar_hip_device_alloc).  (Round 3: physically contiguous
-// allocations, hipDeviceMallocContiguous, made config 3's scatter 27 % slower at every
-// offset)
-static hipError_t dev_malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
 
 int e2sar_hip_device_alloc(e2sar_hip_ctx *ctx, size_t bytes, void **out)
 {
     if (!ctx || !out) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipError_t e = dev_malloc(out, bytes ? bytes : 1);
-    if (e != hipSuccess) return fail(E2SAR_HIP_ERR_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e));
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, nullptr, "hipMalloc", [&](hipStream_t) -> int {
+        const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        return e == hipSuccess ? E2SAR_HIP_OK : alloc_fail(e, "hipMalloc");
+    });
 }
 
 int e2sar_hip_device_free(e2sar_hip_ctx *ctx, void *p)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipFree(p));
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, nullptr, "hipFree(p)", [&](hipStream_t) { return hipFree(p); });
 }
 
 int e2sar_hip_host_alloc(size_t bytes, void **out)
@@ -344,40 +395,36 @@ int e2sar_hip_host_free(void *p)
     return E2SAR_HIP_OK;
 }
 
+// dst <- src on the context's stream, finished on return
+static int memcpy_sync(e2sar_hip_ctx *ctx, void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
+{
+    return ctx_call(ctx, nullptr, "memcpy", [&](hipStream_t s) -> int {
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return E2SAR_HIP_OK;
+    });
+}
+
 int e2sar_hip_memcpy_h2d(e2sar_hip_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return E2SAR_HIP_OK;
+    return memcpy_sync(ctx, dst, src, bytes, hipMemcpyHostToDevice);
 }
 
 int e2sar_hip_memcpy_d2h(e2sar_hip_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return E2SAR_HIP_OK;
-}
-
-int e2sar_hip_memset_d(e2sar_hip_ctx *ctx, void *dst, int value, size_t bytes)
-{
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // a fill kernel, not hipMemsetAsync: the call may be captured into a HIP graph, where
-    // memset nodes misbehave on replay (DESIGN.md 4.4)
-    HIP_TRY(launch_fill_bytes(dst, value, bytes, ctx->stream));
-    return E2SAR_HIP_OK;
+    return memcpy_sync(ctx, dst, src, bytes, hipMemcpyDeviceToHost);
 }
 
 int e2sar_hip_memset_async(e2sar_hip_ctx *ctx, void *dst, int value, size_t bytes, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(launch_fill_bytes(dst, value, bytes, stream ? static_cast<hipStream_t>(stream) : ctx->stream));
-    return E2SAR_HIP_OK;
+    // a fill kernel, not hipMemsetAsync: the call may be captured into a HIP graph, where
+    // memset nodes misbehave on replay (DESIGN.md 4.4)
+    return ctx_call(ctx, stream, "launch_fill_bytes", [&](hipStream_t s) { return launch_fill_bytes(dst, value, bytes, s); });
+}
+
+int e2sar_hip_memset_d(e2sar_hip_ctx *ctx, void *dst, int value, size_t bytes)
+{
+    return e2sar_hip_memset_async(ctx, dst, value, bytes, nullptr);
 }
 
 int e2sar_hip_memcpy_async(e2sar_hip_ctx *ctx, void *dst, const void *src, size_t bytes, int kind, void *stream)
@@ -385,29 +432,25 @@ int e2sar_hip_memcpy_async(e2sar_hip_ctx *ctx, void *dst, const void *src, size_
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
     if (kind < 0 || kind > 2) return fail(E2SAR_HIP_ERR_PARAMETER, "kind must be 0 (H2D), 1 (D2H) or 2 (D2D)");
     if (bytes == 0) return E2SAR_HIP_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, k, s));
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "hipMemcpyAsync(dst, src, bytes, k, s)",
+                    [&](hipStream_t s) { return hipMemcpyAsync(dst, src, bytes, k, s); });
 }
 
 int e2sar_hip_stream_sync(e2sar_hip_ctx *ctx, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(stream ? static_cast<hipStream_t>(stream) : ctx->stream));
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "hipStreamSynchronize", [](hipStream_t s) { return hipStreamSynchronize(s); });
 }
 
 int e2sar_hip_event_create(e2sar_hip_ctx *ctx, void **out)
 {
     if (!ctx || !out) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    *out = e;
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, nullptr, "event_create", [&](hipStream_t) -> int {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        *out = e;
+        return E2SAR_HIP_OK;
+    });
 }
 
 int e2sar_hip_event_destroy(void *event)
@@ -419,14 +462,14 @@ int e2sar_hip_event_destroy(void *event)
 int e2sar_hip_event_record(e2sar_hip_ctx *ctx, void *event, void *stream)
 {
     if (!ctx || !event) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
-    HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(event), stream ? static_cast<hipStream_t>(stream) : ctx->stream));
+    HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(event), stream_of(ctx, stream)));
     return E2SAR_HIP_OK;
 }
 
 int e2sar_hip_stream_wait_event(e2sar_hip_ctx *ctx, void *stream, void *event)
 {
     if (!ctx || !event) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
-    HIP_TRY(hipStreamWaitEvent(stream ? static_cast<hipStream_t>(stream) : ctx->stream, static_cast<hipEvent_t>(event), 0));
+    HIP_TRY(hipStreamWaitEvent(stream_of(ctx, stream), static_cast<hipEvent_t>(event), 0));
     return E2SAR_HIP_OK;
 }
 
@@ -451,22 +494,22 @@ int e2sar_hip_copy_spans(e2sar_hip_ctx *ctx, const e2sar_hip_copy_span *spans, u
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
     if (n == 0) return E2SAR_HIP_OK;
     if (!spans) return fail(E2SAR_HIP_ERR_PARAMETER, "spans is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    for (uint32_t i0 = 0; i0 < n; i0 += kCopySpansPerLaunch) {
-        CopySpans cs{};
-        cs.n = std::min<uint32_t>(kCopySpansPerLaunch, n - i0);
-        uint64_t most = 0;
-        for (uint32_t k = 0; k < cs.n; k++) {
-            const auto &sp = spans[i0 + k];
-            if (sp.bytes && (!sp.src || !sp.dst)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL span pointer");
-            cs.s[k] = CopySpan{reinterpret_cast<uint64_t>(sp.src), reinterpret_cast<uint64_t>(sp.dst), sp.bytes};
-            most = std::max<uint64_t>(most, sp.bytes);
+    return ctx_call(ctx, stream, "copy_spans launch", [&](hipStream_t s) -> int {
+        for (uint32_t i0 = 0; i0 < n; i0 += kCopySpansPerLaunch) {
+            CopySpans cs{};
+            cs.n = std::min<uint32_t>(kCopySpansPerLaunch, n - i0);
+            uint64_t most = 0;
+            for (uint32_t k = 0; k < cs.n; k++) {
+                const auto &sp = spans[i0 + k];
+                if (sp.bytes && (!sp.src || !sp.dst)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL span pointer");
+                cs.s[k] = CopySpan{reinterpret_cast<uint64_t>(sp.src), reinterpret_cast<uint64_t>(sp.dst), sp.bytes};
+                most = std::max<uint64_t>(most, sp.bytes);
+            }
+            const hipError_t e = launch_copy_spans(cs, most, s);
+            if (e != hipSuccess) return hip_fail(e, "copy_spans launch");
         }
-        hipError_t e = launch_copy_spans(cs, most, s);
-        if (e != hipSuccess) return hip_fail(e, "copy_spans launch");
-    }
-    return E2SAR_HIP_OK;
+        return E2SAR_HIP_OK;
+    });
 }
 
 /* ---------------- geometry ---------------- */
@@ -513,38 +556,38 @@ int e2sar_hip_seg_plan(e2sar_hip_seg_event *events, uint32_t nEvents, size_t max
     return E2SAR_HIP_OK;
 }
 
+// Both segmentation entry points: nEvents descriptors, or with devCounts at most that many,
+// the count read by the kernel from d_counts[0].
+static int segment(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_events, bool devCounts, const uint32_t *d_counts,
+                   uint32_t nEvents, uint32_t maxPacketsPerEvent, int lbHdrVersion, uint32_t maxPldLen,
+                   uint8_t *d_packets, uint32_t stride, uint32_t *d_lens, void *stream)
+{
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (nEvents == 0) return E2SAR_HIP_OK;
+    if (!d_events || !d_packets || (devCounts && !d_counts)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
+    return ctx_call(ctx, stream, "seg_kernel launch", [&](hipStream_t s) {
+        return launch_segment(d_events, nEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen, d_packets, stride, d_lens, s,
+                              d_counts);
+    });
+}
+
 int e2sar_hip_segment_batch(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_events,
                             uint32_t nEvents, uint32_t maxPacketsPerEvent, int lbHdrVersion,
                             uint32_t maxPldLen, int eventsDwordAligned, uint8_t *d_packets,
                             uint32_t stride, uint32_t *d_lens, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (nEvents == 0) return E2SAR_HIP_OK;
-    if (!d_events || !d_packets) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
     (void)eventsDwordAligned;        // a hint only: the kernel checks every event's address itself
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipError_t e = launch_segment(d_events, nEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen,
-                                  d_packets, stride, d_lens, s);
-    if (e != hipSuccess) return hip_fail(e, "seg_kernel launch");
-    return E2SAR_HIP_OK;
+    return segment(ctx, d_events, false, nullptr, nEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen, d_packets, stride,
+                   d_lens, stream);
 }
 
 int e2sar_hip_segment_batch_dev(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d_events, const uint32_t *d_counts,
                                 uint32_t maxEvents, uint32_t maxPacketsPerEvent, int lbHdrVersion, uint32_t maxPldLen,
                                 uint8_t *d_packets, uint32_t stride, uint32_t *d_lens, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (maxEvents == 0) return E2SAR_HIP_OK;
-    if (!d_events || !d_counts || !d_packets) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipError_t e = launch_segment(d_events, maxEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen,
-                                  d_packets, stride, d_lens, s, d_counts);
-    if (e != hipSuccess) return hip_fail(e, "seg_kernel launch");
-    return E2SAR_HIP_OK;
+    return segment(ctx, d_events, true, d_counts, maxEvents, maxPacketsPerEvent, lbHdrVersion, maxPldLen, d_packets, stride,
+                   d_lens, stream);
 }
 
 /* ---------------- reassembly ---------------- */
@@ -557,33 +600,25 @@ int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, 
     if (cfg->queueCapacity == 0 || cfg->lostCapacity == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "zero capacity");
     if (cfg->groupSize > 64) return fail(E2SAR_HIP_ERR_PARAMETER, "groupSize must be 0 (auto) or 1..64");
     HIP_TRY(hipSetDevice(ctx->device));
-    auto *r = new e2sar_hip_reas;
-    r->ctx = ctx;
-    r->cfg = *cfg;
+    // a failure below returns through r's destructor, which releases whatever was built
+    auto r = std::make_unique<e2sar_hip_reas>(ctx, *cfg);
     const size_t slotsB = sizeof(ReasSlot) * (size_t)T;
     const size_t ctlB = sizeof(ReasCtl) + (sizeof(ReasShard) + sizeof(ReasOcc)) * kShards;
     const size_t compB = sizeof(e2sar_hip_event_rec) * (size_t)cfg->queueCapacity;
     const size_t lostB = sizeof(e2sar_hip_lost_rec) * (size_t)cfg->lostCapacity;
     const size_t total = slotsB + ctlB + compB + lostB;
-    hipError_t e = hipMalloc(&r->stateMem, total);
-    if (e != hipSuccess) {
-        r->stateMem = nullptr;
-        reas_release(r);
-        return fail(E2SAR_HIP_ERR_MEMORY, std::string("hipMalloc(state): ") + hipGetErrorString(e));
-    }
-    e = dev_malloc(reinterpret_cast<void **>(&r->dev.arena), cfg->arenaBytes ? cfg->arenaBytes : 256);
-    if (e != hipSuccess) {
-        r->dev.arena = nullptr;
-        reas_release(r);
-        return fail(E2SAR_HIP_ERR_MEMORY, std::string("hipMalloc(arena): ") + hipGetErrorString(e));
-    }
+    hipError_t e = dev_alloc(r->state, total);
+    if (e != hipSuccess) return alloc_fail(e, "hipMalloc(state)");
+    // The arenas are plain hipMalloc.  (Round 3: physically contiguous allocations,
+    // hipDeviceMallocContiguous, made config 3's scatter 27 % slower at every offset)
+    const size_t arenaB = cfg->arenaBytes ? cfg->arenaBytes : 256;
+    e = dev_alloc(r->arena[0], arenaB);
+    if (e != hipSuccess) return alloc_fail(e, "hipMalloc(arena)");
     // reas_stream_kernel takes a payload's 16-byte phase in its event buffer from the
     // datagram's bufferOffset alone: event buffers are 256-byte aligned in a 256-byte-aligned arena
-    if ((reinterpret_cast<uintptr_t>(r->dev.arena) & 255u) != 0) {
-        reas_release(r);
-        return fail(E2SAR_HIP_ERR_MEMORY, "arena not 256-byte aligned");
-    }
-    auto *base = static_cast<uint8_t *>(r->stateMem);
+    if ((reinterpret_cast<uintptr_t>(r->arena[0].get()) & 255u) != 0) return fail(E2SAR_HIP_ERR_MEMORY, "arena not 256-byte aligned");
+    auto *base = static_cast<uint8_t *>(r->state.get());
+    r->dev.arena = static_cast<uint8_t *>(r->arena[0].get());
     r->dev.slots = reinterpret_cast<ReasSlot *>(base);
     r->dev.ctl = reinterpret_cast<ReasCtl *>(base + slotsB);
     r->dev.shards = reinterpret_cast<ReasShard *>(base + slotsB + sizeof(ReasCtl));
@@ -598,56 +633,25 @@ int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, 
     r->dev.ownSelf = 0;
     r->dev.groupSize = cfg->groupSize;
     r->alt = r->dev;
+    r->alt.slots = nullptr;          // no alternate table: e2sar_hip_reas_compact refuses
     r->alt.arena = nullptr;
     if (cfg->flags & E2SAR_HIP_REAS_COMPACTABLE) {
-        e = hipMalloc(&r->altSlots, slotsB);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->alt.arena), cfg->arenaBytes ? cfg->arenaBytes : 256);
-        if (e != hipSuccess) {
-            reas_release(r);
-            return fail(E2SAR_HIP_ERR_MEMORY, std::string("hipMalloc(alternate arena): ") + hipGetErrorString(e));
-        }
-        r->alt.slots = reinterpret_cast<ReasSlot *>(r->altSlots);
-        e = hipMemsetAsync(r->altSlots, 0, slotsB, ctx->stream);
-        if (e != hipSuccess) {
-            reas_release(r);
-            return hip_fail(e, "alternate table init");
-        }
-    } else {
-        r->alt.slots = nullptr;
-        r->alt.arena = nullptr;
+        e = dev_alloc(r->altSlots, slotsB);
+        if (e == hipSuccess) e = dev_alloc(r->arena[1], arenaB);
+        if (e != hipSuccess) return alloc_fail(e, "hipMalloc(alternate arena)");
+        r->alt.slots = static_cast<ReasSlot *>(r->altSlots.get());
+        r->alt.arena = static_cast<uint8_t *>(r->arena[1].get());
+        e = hipMemsetAsync(r->altSlots.get(), 0, slotsB, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "alternate table init");
     }
-    e = hipMemsetAsync(r->stateMem, 0, total, ctx->stream);
+    e = hipMemsetAsync(r->state.get(), 0, total, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        reas_release(r);
-        return hip_fail(e, "state init");
-    }
-    ctx->refs.fetch_add(1, std::memory_order_relaxed);          // released by e2sar_hip_reas_destroy
-    *out = r;
+    if (e != hipSuccess) return hip_fail(e, "state init");
+    *out = r.release();
     return E2SAR_HIP_OK;
 }
 
-void e2sar_hip_reas_destroy(e2sar_hip_reas *r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->ctx->device);
-    // launches on any stream (the caller's, a graph replay's) may still use the table, the
-    // arena and the internal buffers: wait for the device before the first hipFree
-    (void)hipDeviceSynchronize();
-    if (r->alt.slots) {
-        // the two tables/arenas may have been swapped: free whichever is not in stateMem
-        auto *base = static_cast<uint8_t *>(r->stateMem);
-        ReasSlot *inState = reinterpret_cast<ReasSlot *>(base);
-        (void)hipFree(r->dev.slots == inState ? static_cast<void *>(r->alt.slots) : static_cast<void *>(r->dev.slots));
-        (void)hipFree(r->alt.arena);
-    }
-    (void)hipFree(r->dev.arena);
-    (void)hipFree(r->stateMem);
-    free_internal(r);
-    e2sar_hip_ctx *ctx = r->ctx;
-    delete r;
-    ctx_release(ctx);
-}
+void e2sar_hip_reas_destroy(e2sar_hip_reas *r) { delete r; }
 
 uint8_t *e2sar_hip_reas_arena(e2sar_hip_reas *r) { return r ? r->dev.arena : nullptr; }
 
@@ -660,9 +664,9 @@ static int ro_prepare(e2sar_hip_reas *r, hipStream_t s, uint32_t n)
     // use); a new buffer starts them at zero
     auto &sc = r->scratch[s];
     bool grew = false;
-    if (int rc = grow(r, s, sc.roScratch, sc.roScratchBytes, ro_scratch_bytes(n, r->dev.tableSlots), &grew)) return rc;
-    if (grew) HIP_TRY(hipMemsetAsync(sc.roScratch, 0, ro_zero_bytes(r->dev.tableSlots), s));
-    else if (sc.roDirty) HIP_TRY(launch_fill_bytes(sc.roScratch, 0, ro_zero_bytes(r->dev.tableSlots), s));  // capture-safe
+    if (int rc = grow(r, s, sc.ro, ro_scratch_bytes(n, r->dev.tableSlots), &grew)) return rc;
+    if (grew) HIP_TRY(hipMemsetAsync(sc.ro.mem.get(), 0, ro_zero_bytes(r->dev.tableSlots), s));
+    else if (sc.roDirty) HIP_TRY(launch_fill_bytes(sc.ro.mem.get(), 0, ro_zero_bytes(r->dev.tableSlots), s));  // capture-safe
     sc.roDirty = false;
     return E2SAR_HIP_OK;
 }
@@ -672,7 +676,7 @@ static hipError_t ro_classify(e2sar_hip_reas *r, hipStream_t s, const uint8_t *p
                               uint32_t n, uint64_t now, void *work)
 {
     auto &sc = r->scratch[s];
-    const hipError_t e = launch_ro_classify(r->dev, pk, stride, lens, n, now, work, sc.roScratch, sc.roScratchBytes, s);
+    const hipError_t e = launch_ro_classify(r->dev, pk, stride, lens, n, now, work, sc.ro.mem.get(), sc.ro.bytes, s);
     if (e != hipSuccess) sc.roDirty = true;
     return e;
 }
@@ -691,10 +695,11 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
         if (ref_order(r)) {
             // classify in arrival order into the internal work buffer, then the scatter kernel
             if (int rc = ro_prepare(r, s, nPackets)) return rc;
-            if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
-            hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork);
+            if (int rc = grow(r, s, sc.work, work_bytes(nPackets))) return rc;
+            void *work = sc.work.mem.get();
+            hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, work);
             if (e == hipSuccess)
-                e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, cold_loads(r, nPackets, stride));
+                e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, work, s, cold_loads(r, nPackets, stride));
             if (e != hipSuccess) return hip_fail(e, "reference-order reassembly launch");
             return E2SAR_HIP_OK;
         }
@@ -705,9 +710,10 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
         // datagrams, BASELINE config 3): 1116 GiB/s fused vs 1302 split.  Internal work buffer
         // of this stream, grown on first use (outside graph capture).
         if ((uint64_t)nPackets * stride > kFusedMaxBytes) {
-            if (int rc = grow(r, s, sc.roWork, sc.roWorkBytes, work_bytes(nPackets))) return rc;
-            hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, sc.roWork, s);
-            if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, sc.roWork, s, true);
+            if (int rc = grow(r, s, sc.work, work_bytes(nPackets))) return rc;
+            void *work = sc.work.mem.get();
+            hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, work, s);
+            if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, work, s, true);
             if (e != hipSuccess) return hip_fail(e, "reassembly launch (split form)");
             return E2SAR_HIP_OK;
         }
@@ -760,8 +766,7 @@ static int segreas(e2sar_hip_ctx *ctx, const e2sar_hip_segreas_batch *batches, u
         const e2sar_hip_segreas_batch &x = batches[b];
         if (x.nEvents == 0 || x.nPackets == 0) continue;
         if (!x.d_events || !x.d_packets || !x.d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
-        if (((uintptr_t)x.d_packets & 15u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "packet buffer not 16-byte aligned");
-        if ((uint64_t)x.nPackets * (stride >> 4) > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "batch too large");
+        if (int rc = check_packets(x.d_packets, stride, x.nPackets)) return rc;
         for (uint32_t c = 0; c < b; c++)
             if (batches[c].d_packets == x.d_packets && batches[c].nPackets)
                 return fail(E2SAR_HIP_ERR_PARAMETER, "batches of one launch need distinct packet buffers");
@@ -778,13 +783,13 @@ static int segreas(e2sar_hip_ctx *ctx, const e2sar_hip_segreas_batch *batches, u
     if (cb.nb == 0) return E2SAR_HIP_OK;
     return reas_launch(r, stream, "segreas_kernel launch", [&](hipStream_t s) -> int {
         auto &sc = r->scratch[s];
-        if (int rc = grow(r, s, sc.tiles, sc.tilesBytes, 4ull * words)) return rc;
-        for (uint32_t b = 0; b < cb.nb; b++)
-            cb.b[b].tiles = static_cast<uint32_t *>(sc.tiles) + reinterpret_cast<uintptr_t>(cb.b[b].tiles);
+        if (int rc = grow(r, s, sc.tiles, 4ull * words)) return rc;
+        auto *tiles = static_cast<uint32_t *>(sc.tiles.mem.get());
+        for (uint32_t b = 0; b < cb.nb; b++) cb.b[b].tiles = tiles + reinterpret_cast<uintptr_t>(cb.b[b].tiles);
         // the launch's ready counters start at 0: zeroed by a kernel (capture-safe)
         // before every launch, so a group that gave up waiting in an earlier launch (error bit 4)
         // cannot leave a count behind for this one
-        hipError_t e = launch_zero_words(sc.tiles, words, s);
+        hipError_t e = launch_zero_words(tiles, words, s);
         if (e == hipSuccess) e = launch_segreas(cb, lbHdrVersion, maxPldLen, stride, r->dev, now_ms, s);
         if (e != hipSuccess) return hip_fail(e, "segreas_kernel launch");
         return E2SAR_HIP_OK;
@@ -917,9 +922,13 @@ static int wait_launches(e2sar_hip_reas *r)
         HIP_TRY(hipDeviceSynchronize());
         return E2SAR_HIP_OK;
     }
-    if (!r->waitEv) HIP_TRY(hipEventCreateWithFlags(&r->waitEv, hipEventDisableTiming));
+    if (!r->waitEv) {
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        r->waitEv.reset(ev);
+    }
     for (auto it = r->streams.begin(); it != r->streams.end();) {
-        const hipError_t e = hipEventRecord(r->waitEv, *it);
+        const hipError_t e = hipEventRecord(r->waitEv.get(), *it);
         if (e == hipErrorInvalidHandle || e == hipErrorContextIsDestroyed || e == hipErrorInvalidResourceHandle) {
             // a stream destroyed without e2sar_hip_reas_forget_stream: its work finished when
             // it was destroyed; its scratch goes with it
@@ -929,12 +938,11 @@ static int wait_launches(e2sar_hip_reas *r)
             continue;
         }
         if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-        HIP_TRY(hipEventSynchronize(r->waitEv));
+        HIP_TRY(hipEventSynchronize(r->waitEv.get()));
         ++it;
     }
     // every launch of this reassembler has finished and none was captured, so no kernel and
-    // no graph can still hold a buffer that an earlier growth retired
-    for (void *p : r->retired) (void)hipFree(p);
+    // no graph can still hold a buffer that an earlier growth retired: freed
     r->retired.clear();
     return E2SAR_HIP_OK;
 }
@@ -956,27 +964,11 @@ static int read_ctl_occ(e2sar_hip_reas *r, ReasCtl &c)
 
 // Snapshot of the control block after every launch of this reassembler finished
 // (wait_launches), so the read-modify-write of the list counts in poll / lost_poll cannot
-// race a kernel's completion atomics.  With `sum` (get_stats) the per-packet shards are
-// summed into it and the occupancy counters folded into c; poll / lost_poll need only the
-// list counts.
-static int read_ctl(e2sar_hip_reas *r, ReasCtl &c, ReasShard *sum = nullptr)
+// race a kernel's completion atomics.
+static int read_ctl(e2sar_hip_reas *r, ReasCtl &c)
 {
     if (int rc = wait_launches(r)) return rc;
-    if (!sum) {
-        HIP_TRY(hipMemcpy(&c, r->dev.ctl, sizeof(ReasCtl), hipMemcpyDeviceToHost));
-    } else {
-        if (int rc = read_ctl_occ(r, c)) return rc;
-        std::vector<ReasShard> sh(kShards);
-        HIP_TRY(hipMemcpy(sh.data(), r->dev.shards, sizeof(ReasShard) * kShards, hipMemcpyDeviceToHost));
-        *sum = ReasShard{};
-        for (const auto &x : sh) {
-            sum->totalPackets += x.totalPackets;
-            sum->totalBytes += x.totalBytes;
-            sum->badHeaderDiscards += x.badHeaderDiscards;
-            sum->dataErrCnt += x.dataErrCnt;
-            sum->eventSuccess += x.eventSuccess;
-        }
-    }
+    HIP_TRY(hipMemcpy(&c, r->dev.ctl, sizeof(ReasCtl), hipMemcpyDeviceToHost));
     return E2SAR_HIP_OK;
 }
 
@@ -996,40 +988,37 @@ static int slide_down(Rec *base, uint32_t n, uint32_t avail)
     return E2SAR_HIP_OK;
 }
 
-extern "C" {
-
-int e2sar_hip_reas_poll(e2sar_hip_reas *r, e2sar_hip_event_rec *out, uint32_t cap, uint32_t *nOut)
+// Hand the first min(cap, queued) records of one of the two device lists to the caller and
+// keep the rest queued: the list, its count in ReasCtl and its capacity.
+template <typename Rec>
+static int poll_list(e2sar_hip_reas *r, Rec *ReasDev::*list, uint32_t ReasCtl::*count, uint32_t ReasDev::*capacity,
+                     Rec *out, uint32_t cap, uint32_t *nOut)
 {
     if (!r || !nOut || (!out && cap)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
     std::lock_guard<std::mutex> lk(r->mu);
     ReasCtl c;
-    int rc = read_ctl(r, c);
-    if (rc) return rc;
-    const uint32_t avail = std::min(c.nCompleted, r->dev.queueCapacity);
+    if (int rc = read_ctl(r, c)) return rc;
+    Rec *recs = r->dev.*list;
+    const uint32_t avail = std::min(c.*count, r->dev.*capacity);
     const uint32_t n = std::min(avail, cap);
-    if (n) HIP_TRY(hipMemcpy(out, r->dev.completed, sizeof(e2sar_hip_event_rec) * n, hipMemcpyDeviceToHost));
-    if (int rc2 = slide_down(r->dev.completed, n, avail)) return rc2;
+    if (n) HIP_TRY(hipMemcpy(out, recs, sizeof(Rec) * n, hipMemcpyDeviceToHost));
+    if (int rc = slide_down(recs, n, avail)) return rc;
     const uint32_t left = avail - n;
-    HIP_TRY(hipMemcpy(&r->dev.ctl->nCompleted, &left, sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(&(r->dev.ctl->*count), &left, sizeof(uint32_t), hipMemcpyHostToDevice));
     *nOut = n;
     return E2SAR_HIP_OK;
 }
 
+extern "C" {
+
+int e2sar_hip_reas_poll(e2sar_hip_reas *r, e2sar_hip_event_rec *out, uint32_t cap, uint32_t *nOut)
+{
+    return poll_list(r, &ReasDev::completed, &ReasCtl::nCompleted, &ReasDev::queueCapacity, out, cap, nOut);
+}
+
 int e2sar_hip_reas_lost_poll(e2sar_hip_reas *r, e2sar_hip_lost_rec *out, uint32_t cap, uint32_t *nOut)
 {
-    if (!r || !nOut || (!out && cap)) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
-    std::lock_guard<std::mutex> lk(r->mu);
-    ReasCtl c;
-    int rc = read_ctl(r, c);
-    if (rc) return rc;
-    const uint32_t avail = std::min(c.nLost, r->dev.lostCapacity);
-    const uint32_t n = std::min(avail, cap);
-    if (n) HIP_TRY(hipMemcpy(out, r->dev.lost, sizeof(e2sar_hip_lost_rec) * n, hipMemcpyDeviceToHost));
-    if (int rc2 = slide_down(r->dev.lost, n, avail)) return rc2;
-    const uint32_t left = avail - n;
-    HIP_TRY(hipMemcpy(&r->dev.ctl->nLost, &left, sizeof(uint32_t), hipMemcpyHostToDevice));
-    *nOut = n;
-    return E2SAR_HIP_OK;
+    return poll_list(r, &ReasDev::lost, &ReasCtl::nLost, &ReasDev::lostCapacity, out, cap, nOut);
 }
 
 int e2sar_hip_reas_get_stats(e2sar_hip_reas *r, e2sar_hip_reas_stats *out)
@@ -1037,9 +1026,19 @@ int e2sar_hip_reas_get_stats(e2sar_hip_reas *r, e2sar_hip_reas_stats *out)
     if (!r || !out) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
     std::lock_guard<std::mutex> lk(r->mu);
     ReasCtl c;
-    ReasShard t;
-    int rc = read_ctl(r, c, &t);
-    if (rc) return rc;
+    if (int rc = wait_launches(r)) return rc;
+    if (int rc = read_ctl_occ(r, c)) return rc;
+    // the per-packet counters: summed over the shards
+    std::vector<ReasShard> sh(kShards);
+    HIP_TRY(hipMemcpy(sh.data(), r->dev.shards, sizeof(ReasShard) * kShards, hipMemcpyDeviceToHost));
+    ReasShard t{};
+    for (const auto &x : sh) {
+        t.totalPackets += x.totalPackets;
+        t.totalBytes += x.totalBytes;
+        t.badHeaderDiscards += x.badHeaderDiscards;
+        t.dataErrCnt += x.dataErrCnt;
+        t.eventSuccess += x.eventSuccess;
+    }
     out->enqueueLoss = c.enqueueLoss;
     out->reassemblyLoss = c.reassemblyLoss;
     out->eventSuccess = c.eventSuccess + t.eventSuccess;
@@ -1150,18 +1149,14 @@ static int route(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_t stride, 
                  uint8_t *d_sendPackets, uint32_t *d_sendLens, uint32_t *d_counts, void *d_workspace,
                  size_t workspaceBytes, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (int rc = check_world(world, self)) return rc;
-    if ((stride & 15u) || stride < 48u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16, >= 48");
+    if (int rc = check_route(ctx, world, self, stride)) return rc;
     if (nPackets && (!d_packets || !d_lens || !d_sendPackets || !d_sendLens || !d_counts || !d_workspace))
         return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
     if (workspaceBytes < route_workspace_bytes(nPackets, world)) return fail(E2SAR_HIP_ERR_PARAMETER, "workspace too small");
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipError_t e = launch_route(d_packets, stride, d_lens, nPackets, withLBHeader, world, self, excludeSelf,
-                                d_sendPackets, d_sendLens, d_counts, d_workspace, s);
-    if (e != hipSuccess) return hip_fail(e, "route launch");
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "route launch", [&](hipStream_t s) {
+        return launch_route(d_packets, stride, d_lens, nPackets, withLBHeader, world, self, excludeSelf, d_sendPackets,
+                            d_sendLens, d_counts, d_workspace, s);
+    });
 }
 
 extern "C" {
@@ -1189,9 +1184,7 @@ int e2sar_hip_route_append(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_
                            uint8_t *d_sendPackets, uint32_t *d_sendLens, uint32_t capPerRank, uint32_t *d_running,
                            void *d_workspace, size_t workspaceBytes, void *stream)
 {
-    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
-    if (int rc = check_world(world, self)) return rc;
-    if ((stride & 15u) || stride < 48u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16, >= 48");
+    if (int rc = check_route(ctx, world, self, stride)) return rc;
     if (capPerRank == 0 || (uint64_t)capPerRank * world > 0xFFFFFFFFull)
         return fail(E2SAR_HIP_ERR_PARAMETER, "capPerRank must be > 0 and capPerRank * world < 2^32");
     if (!d_running) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL running counters");
@@ -1199,12 +1192,10 @@ int e2sar_hip_route_append(e2sar_hip_ctx *ctx, const uint8_t *d_packets, uint32_
         return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
     (void)d_workspace;
     (void)workspaceBytes;                  // one launch, no workspace (kept in the signature for callers)
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipError_t e = launch_route_append(d_packets, stride, d_lens, nPackets, withLBHeader, world, self, foreignOnly ? 1 : 0,
-                                       d_sendPackets, d_sendLens, capPerRank, d_running, s);
-    if (e != hipSuccess) return hip_fail(e, "route launch");
-    return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "route launch", [&](hipStream_t s) {
+        return launch_route_append(d_packets, stride, d_lens, nPackets, withLBHeader, world, self, foreignOnly ? 1 : 0,
+                                   d_sendPackets, d_sendLens, capPerRank, d_running, s);
+    });
 }
 
 int e2sar_hip_reas_set_owner(e2sar_hip_reas *r, uint32_t world, uint32_t self)

@@ -253,8 +253,10 @@ uint8_t *e2sar_hip_reas_arena(e2sar_hip_reas *r);
  * sit in the Infinity Cache) classify + scatter launches through an internal work buffer.
  * Internal buffers (this form, reference order) are kept per stream, so batches may be launched on several streams at once; they grow on first
  * use for a size, never inside a graph capture (LOGIC error: run one batch of the largest
- * size on the stream first), and an outgrown buffer stays allocated until destroy, so a
- * graph captured earlier keeps valid addresses.
+ * size on the stream first).  Once a launch has been captured, an outgrown buffer stays
+ * allocated until destroy, so a graph captured earlier keeps valid addresses; before that it
+ * is freed by the next call that waits for this reassembler's launches (poll, lost_poll,
+ * get_stats, compact, recycle without force).
  * Asynchronous on `stream` (NULL = the context stream). */
 int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride,
                                const uint32_t *d_lens, uint32_t nPackets, uint64_t now_ms,

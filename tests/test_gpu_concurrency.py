@@ -258,6 +258,134 @@ def test_forget_stream_then_destroy(hip):
     assert R.stats().eventSuccess == ost["eventSuccess"]
 
 
+MP80, STRIDE80 = 16, 64          # MTU 80: 16-byte payloads in 64-byte datagram slots
+HISTORY = ("eventSuccess", "totalPackets", "totalBytes", "badHeaderDiscards", "dataErrCnt", "enqueueLoss",
+           "reassemblyLoss")
+
+
+def _mtu80_datagrams(sizes, seed):
+    """Events of the given sizes segmented by the oracle at MTU 80, event after event:
+    (packets[n, 64], lens[n], first datagram of every event and n)."""
+    rng = np.random.default_rng(seed)
+    parts = [O.segment_event(rng.integers(0, 256, s, dtype=np.uint8), k, 4321, 1 + k, (1 << 48) + k, 2, MP80, STRIDE80)
+             for k, s in enumerate(sizes)]
+    first = np.cumsum([0] + [len(ln) for _, ln in parts])
+    return np.concatenate([pk for pk, _ in parts]), np.concatenate([ln for _, ln in parts]), first
+
+
+def _upload80(ctx, pk, ln):
+    torch = _torch()
+    dpk = torch.from_numpy(np.ascontiguousarray(pk).reshape(-1)).to(ctx.torch_device)
+    dln = torch.from_numpy(np.ascontiguousarray(ln, np.uint32).view(np.int32).copy()).to(ctx.torch_device)
+    return dpk, dln
+
+
+def _poll_as_oracle(R, ref):
+    """Poll R and pop the oracle: the same events (key, bytes, numFragments) and the same seven
+    history counters.  Returns the number of events."""
+    got = sorted(((r.eventNum, r.dataId), R.event_bytes(r), r.numFragments) for r in R.poll())
+    want = sorted(((e, d), b, f) for b, e, d, f in ref.pop_all_frags(1 << 16))
+    assert got == want
+    st, ost = R.stats(), ref.stats()
+    for f in HISTORY:
+        assert getattr(st, f) == ost[f], (f, getattr(st, f), ost[f])
+    return len(got)
+
+
+def _small_life(ctx):
+    """A 64-slot reassembler on ctx: one batch of 3 events of 67 bytes, as the oracle; closed."""
+    from e2sar_amd import sar
+    pk, ln, _ = _mtu80_datagrams([67] * 3, 0xA11)
+    dpk, dln = _upload80(ctx, pk, ln)
+    R = sar.DeviceReassembler(ctx, with_lb_header=True, table_slots=64, arena_bytes=1 << 20)
+    R.reassemble(dpk, STRIDE80, dln, len(ln))
+    ref = O.Reassembler(True)
+    ref.push_batch(pk, ln)
+    assert _poll_as_oracle(R, ref) == 3
+    R.close()
+
+
+def test_failed_create_leaves_the_context_usable(hip):
+    """e2sar_hip_reas_create with an arena the runtime refuses by size (2^62 bytes; nothing
+    runs on the device), plain and COMPACTABLE: ERR_MEMORY, 'hipMalloc(arena): ...', no handle,
+    whatever it had allocated released.  The same context then serves a reassembler whose
+    first launch must not report the allocation's error, and a context created afterwards
+    goes with its reassembler."""
+    import ctypes as C
+    from e2sar_amd import _capi, sar
+    from e2sar_amd._capi import check, lib
+    for flags in (0, _capi.REAS_COMPACTABLE):
+        cfg = _capi.ReasConfig(1, 64, 4096, 4096, 1 << 62, flags, 0)
+        h = C.c_void_p()
+        with pytest.raises(_capi.E2SARHipError) as ei:
+            check(lib().e2sar_hip_reas_create(hip.handle, C.byref(cfg), C.byref(h)))
+        assert ei.value.code == _capi.ERR_MEMORY
+        assert ei.value.msg.startswith("hipMalloc(arena): "), ei.value.msg
+        assert not h.value
+    p = C.c_void_p()
+    with pytest.raises(_capi.E2SARHipError) as ei:                  # the same refusal, not through a reassembler
+        check(lib().e2sar_hip_device_alloc(hip.handle, 1 << 62, C.byref(p)))
+    assert ei.value.code == _capi.ERR_MEMORY and ei.value.msg.startswith("hipMalloc: "), ei.value.msg
+    _small_life(hip)
+    ctx = sar.Context(0)
+    _small_life(ctx)
+    ctx.close()
+
+
+def test_every_owner_in_one_life(hip):
+    """What a reassembler owns, all in one life: per-stream scratch on a stream of our own
+    (reference order), both internal buffers outgrown and retired (8 datagrams, then 1,200:
+    the sort scratch is about 524 bytes per table slot + 56 per datagram, grown with a quarter
+    of headroom), the tables swapped by one compaction while every event is in progress, the
+    retired buffers freed at the next snapshot, then the batch that completes every event.
+    Events, numFragments and the history counters as the oracle's, fed the same datagrams in
+    the same order; then forget_stream, the stream destroyed, the reassembler closed."""
+    import ctypes as C
+    torch = _torch()
+    from e2sar_amd import _capi, sar
+    from e2sar_amd._capi import check, lib
+    n_ev = 48
+    pk, ln, first = _mtu80_datagrams([650 + 7 * k for k in range(n_ev)], 0x0B0E)
+    n = len(ln)
+    # arrival order: every event's offset-0 fragment (in the reference it starts the event
+    # anew), then the others shuffled, but one fragment of every event held back to the very
+    # end, so no event completes before the compaction (which refuses while records are unpolled)
+    rng = np.random.default_rng(0x0B0E)
+    held = np.array([rng.integers(first[k] + 1, first[k + 1]) for k in range(n_ev)])
+    rest = np.setdiff1d(np.arange(n), np.concatenate([first[:-1], held]))
+    order = np.concatenate([rng.permutation(first[:-1]), rng.permutation(rest), rng.permutation(held)])
+    pk, ln = pk[order], ln[order]
+    cuts = [0, 8, 8 + 1200, n]
+    assert n - cuts[2] >= 1024 + n_ev
+    dpk, dln = _upload80(hip, pk, ln)
+    R = sar.DeviceReassembler(hip, with_lb_header=True, table_slots=64, arena_bytes=1 << 20, compactable=True,
+                              flags=_capi.REAS_REFERENCE_ORDER)
+    ref = O.Reassembler(True)
+    torch.cuda.synchronize()
+    s1 = C.c_void_p()
+    check(lib().e2sar_hip_stream_create(0, C.byref(s1)))
+
+    def batch(a, b):
+        check(lib().e2sar_hip_reassemble_batch(R.handle, C.c_void_p(dpk[a * STRIDE80:].data_ptr()), STRIDE80,
+                                               C.c_void_p(dln[a:].data_ptr()), b - a, 0, s1))
+        ref.push_batch(pk[a:b], ln[a:b])
+
+    batch(cuts[0], cuts[1])
+    batch(cuts[1], cuts[2])
+    before = R.arena_ptr
+    R.compact()
+    assert R.arena_ptr != before
+    assert _poll_as_oracle(R, ref) == 0
+    st = R.stats()
+    assert st.inProgress == ref.stats()["inProgress"] == n_ev
+    batch(cuts[2], cuts[3])
+    assert _poll_as_oracle(R, ref) == n_ev
+    assert R.stats().inProgress == ref.stats()["inProgress"] == 0
+    check(lib().e2sar_hip_reas_forget_stream(R.handle, s1))
+    check(lib().e2sar_hip_stream_destroy(s1))
+    R.close()
+
+
 def test_context_destroyed_before_its_reassembler(hip):
     """A garbage collector tearing down a reference cycle destroys a Context and the
     DeviceReassembler made on it in either order; the reassembler holds a reference on the
