@@ -214,12 +214,15 @@ __device__ Classified classify_wave(const ReasDev &R, const RawHdr &raw, uint32_
     return out;
 }
 
-// True when this run tail's add brought curBytes to the event length (cpp:403).
+// True when this run tail's add brought curBytes to the event length (cpp:403).  An add of
+// no bytes brings it nowhere: it completes only an event of length 0, as that event's first
+// add.  (An empty fragment that found curBytes already at the length -- its event whole but
+// not yet marked DONE -- met the length a second time: the event was delivered twice.)
 __device__ __forceinline__ bool completes(const Classified &c)
 {
     if (!c.tailAdd) return false;
     const uint64_t nb = (c.old & kAccBytesMask) + c.rb;
-    return c.rc > 0 && nb == c.sbytes;
+    return c.rc > 0 && nb == c.sbytes && (c.rb > 0 || c.old == 0);
 }
 
 __device__ __forceinline__ void classify_finish(const ReasDev &R, const Classified &c)
