@@ -89,6 +89,21 @@ class EventRec(C.Structure):
     ]
 
 
+class CollectRec(C.Structure):
+    _fields_ = [
+        ("eventNum", C.c_uint64),
+        ("outOffset", C.c_uint64),
+        ("bytes", C.c_uint32),
+        ("dataId", C.c_uint16),
+        ("flags", C.c_uint16),
+        ("numFragments", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+COLLECT_TRUNCATED = 1         # CollectRec.flags, row mode: the event is longer than the pitch
+
+
 class LostRec(C.Structure):
     _fields_ = [
         ("eventNum", C.c_uint64),
@@ -121,6 +136,7 @@ class ReasStats(C.Structure):
 assert C.sizeof(SegEvent) == 40
 assert C.sizeof(EventRec) == 32
 assert C.sizeof(LostRec) == 24
+assert C.sizeof(CollectRec) == 32
 
 vp = C.c_void_p
 u8p = C.c_void_p
@@ -166,6 +182,7 @@ SIGNATURES = {
     "e2sar_hip_segment_batch_dev": (i, [vp, vp, vp, u32, u32, i, u32, vp, u32, vp, vp]),
     "e2sar_hip_segment_batch_recycle": (i, [vp, vp, u32, u32, i, u32, i, vp, u32, vp, vp, i, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),
+    "e2sar_hip_reas_collect": (i, [vp, u32, u32, vp, u64, u32, u32, vp, vp, vp]),
     "e2sar_hip_reas_create": (i, [vp, C.POINTER(ReasConfig), C.POINTER(vp)]),
     "e2sar_hip_reas_destroy": (None, [vp]),
     "e2sar_hip_reas_arena": (vp, [vp]),

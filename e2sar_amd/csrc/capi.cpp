@@ -827,6 +827,24 @@ int e2sar_hip_relay_plan(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t maxEv
     });
 }
 
+int e2sar_hip_reas_collect(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t maxEvents, uint8_t *d_out,
+                           uint64_t outBytes, uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index,
+                           uint64_t *d_counts, void *stream)
+{
+    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
+    if (!d_out || !d_index || !d_counts) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (maxEvents == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxEvents is 0");
+    if (((uintptr_t)d_out & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "output buffer not 256-byte aligned");
+    if (pitch & 15u) return fail(E2SAR_HIP_ERR_PARAMETER, "pitch must be a multiple of 16");
+    if (align == 0) align = 256;
+    if (align < 16 || align > 4096 || (align & (align - 1)))
+        return fail(E2SAR_HIP_ERR_PARAMETER, "align must be 0 or a power of two in [16, 4096]");
+    // no internal buffer, no memset node: the two launches capture as they are
+    return reas_launch(r, stream, "collect launch", [&](hipStream_t s) {
+        return launch_collect(r->dev, firstRecord, maxEvents, d_out, outBytes, pitch, align, d_index, d_counts, s);
+    });
+}
+
 size_t e2sar_hip_reas_work_bytes(uint32_t nPackets) { return work_bytes(nPackets); }
 
 int e2sar_hip_reas_classify(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride,

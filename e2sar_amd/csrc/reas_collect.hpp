@@ -1,0 +1,192 @@
+// reas_collect.hpp -- device-side delivery: the events a reassembler completed, packed into a caller's device buffer.
+#pragma once
+
+#include "dev_access.hpp"
+#include "reas_upkeep.hpp"
+
+namespace e2sar_amd {
+
+// ---------------------------------------------------------------------------------
+// collect: completed records [first, first + avail) leave the arena without a host round
+// trip, as one ragged packed buffer (pitch == 0: event i at the sum of the earlier events'
+// lengths, each rounded up to `align`) or as fixed-pitch rows (event i at i * pitch, cut to
+// pitch bytes and zero-filled up to it).  Two launches: collect_plan_kernel lays the events
+// out and writes the index table and the counts; collect_copy_kernel moves the bytes, one
+// 8-KiB piece per workgroup as copy_spans_kernel does, on a grid the host sizes from bounds
+// alone -- it knows neither how many events there are nor how long they are.
+
+__host__ __device__ constexpr uint32_t collect_pieces(uint64_t extent)
+{
+    return (uint32_t)((extent + kCopyPiece - 1u) / kCopyPiece);
+}
+
+// The arena bytes are read once: streaming loads, as copy_spans_kernel's (the A/B against
+// cache-allocating loads is in DESIGN.md 4.8).
+__device__ __forceinline__ u32x4 collect_ld16(const uint8_t *p) { return ld16_nt(p); }
+
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan_shfl(T v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(v, o);
+        if (lane >= o) v += y;
+    }
+    return v;
+}
+
+// One workgroup, 256 records per step (relay_plan_kernel's shape).  Per step: a block-wide
+// scan of the padded extents on top of a 64-bit carry gives every record its offset; the
+// capacity cut is the first record whose end would pass outBytes, and nothing after it is
+// taken, even if it would fit (record order is kept); a second scan, over the taken records
+// only, gives each its first copy piece -- the exclusive prefix of ceil(extent / 8 KiB),
+// kept in the index record's `reserved` word, where collect_copy_kernel searches it.
+__global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_t first, uint32_t maxEvents,
+                                                              uint64_t outBytes, uint32_t pitch, uint32_t align,
+                                                              e2sar_hip_collect_rec *__restrict__ index,
+                                                              uint64_t *__restrict__ counts)
+{
+    constexpr uint32_t kWaves = kBlock / 64;
+    __shared__ uint64_t wavePad[kWaves], waveTaken[kWaves], waveCopied[kWaves];
+    __shared__ uint32_t wavePieces[kWaves], waveCut[kWaves];
+    __shared__ uint32_t sAvail, sLimit;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        uint32_t stored = ld_agent(&R.ctl->nCompleted);
+        if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
+        const uint32_t avail = stored > first ? stored - first : 0u;
+        uint32_t limit = avail < maxEvents ? avail : maxEvents;
+        if (pitch && outBytes / pitch < limit) limit = (uint32_t)(outBytes / pitch);
+        sAvail = avail;
+        sLimit = limit;
+    }
+    __syncthreads();
+    const uint32_t limit = sLimit;
+    uint32_t n = limit, pieces = 0;
+    uint64_t carry = 0, copied = 0;                        // bytes of `out` spanned, event bytes copied
+    for (uint32_t b0 = 0; b0 < limit; b0 += kBlock) {
+        const uint32_t i = b0 + threadIdx.x;
+        const bool active = i < limit;
+        e2sar_hip_event_rec rec{};
+        if (active) rec = R.completed[first + i];
+        const uint64_t extent = pitch ? (uint64_t)pitch : (uint64_t)rec.bytes;
+        const uint64_t pad = !active ? 0ull : pitch ? (uint64_t)pitch : (((uint64_t)rec.bytes + align - 1u) & ~(uint64_t)(align - 1u));
+        const uint64_t incPad = wave_incl_scan_shfl(pad, lane);
+        if (lane == 63) wavePad[wv] = incPad;
+        __syncthreads();
+        uint64_t off = carry + incPad - pad;
+        for (uint32_t w = 0; w < wv; w++) off += wavePad[w];
+        // rows were cut by outBytes / pitch above; a ragged event must end inside the buffer
+        const bool fits = !active || pitch || off + rec.bytes <= outBytes;
+        const unsigned long long miss = __ballot(!fits);
+        if (lane == 0) waveCut[wv] = miss ? b0 + wv * 64u + (uint32_t)__builtin_ctzll(miss) : ~0u;
+        __syncthreads();
+        uint32_t cut = ~0u;
+        for (uint32_t w = 0; w < kWaves; w++) cut = waveCut[w] < cut ? waveCut[w] : cut;
+        const bool taken = active && i < cut;
+        const uint32_t np = taken ? collect_pieces(extent) : 0u;
+        const uint64_t cp = !taken ? 0ull : rec.bytes < extent ? (uint64_t)rec.bytes : extent;
+        const uint32_t incNp = wave_incl_scan_shfl(np, lane);
+        const uint64_t incTaken = wave_incl_scan_shfl(taken ? pad : 0ull, lane);
+        const uint64_t incCp = wave_incl_scan_shfl(cp, lane);
+        if (lane == 63) {
+            wavePieces[wv] = incNp;
+            waveTaken[wv] = incTaken;
+            waveCopied[wv] = incCp;
+        }
+        __syncthreads();
+        if (taken) {
+            uint32_t before = pieces;
+            for (uint32_t w = 0; w < wv; w++) before += wavePieces[w];
+            e2sar_hip_collect_rec o;
+            o.eventNum = rec.eventNum;
+            o.outOffset = off;
+            o.bytes = rec.bytes;
+            o.dataId = rec.dataId;
+            o.flags = (uint16_t)((pitch && rec.bytes > pitch) ? E2SAR_HIP_COLLECT_TRUNCATED : 0);
+            o.numFragments = rec.numFragments;
+            o.reserved = before + incNp - np;
+            index[i] = o;
+        }
+        for (uint32_t w = 0; w < kWaves; w++) {
+            pieces += wavePieces[w];
+            carry += waveTaken[w];
+            copied += waveCopied[w];
+        }
+        if (cut != ~0u) {                                   // the same in every thread
+            n = cut;
+            break;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        counts[0] = n;
+        counts[1] = carry;
+        counts[2] = sAvail - n;
+        counts[3] = copied;
+    }
+}
+
+// One workgroup per 8-KiB piece of one event's extent (its bytes, or its row of `pitch`).
+// The grid comes from bounds, so a workgroup first reads what collect_plan_kernel wrote on
+// the stream before it: the event count, and from the last index record the piece total; a
+// workgroup past the total exits.  The others find their event -- a row's by division, a
+// ragged event's by binary search over the piece prefix, log2(n) workgroup-uniform loads of a
+// table that sits in L2 -- and copy the piece as copy_spans_kernel does: every thread issues
+// its kCopyU 16-byte loads before any store.  Arena event buffers are 256-byte aligned and
+// outOffset at least 16-byte aligned, so there is no unaligned form.  Whole 16-byte chunks
+// of the event are copied, the last bytes mod 16 go as byte stores (no load or store touches
+// a byte past the event), and in row mode everything from the event's end to the pitch is
+// stored as zeros.  The loop is a guard, not the plan: should the bounds ever undercount the
+// pieces, the grid strides over the rest.
+__global__ __launch_bounds__(kBlock) void collect_copy_kernel(const uint8_t *__restrict__ arena,
+                                                              const e2sar_hip_event_rec *__restrict__ completed,
+                                                              uint8_t *__restrict__ out, uint32_t pitch,
+                                                              const e2sar_hip_collect_rec *__restrict__ index,
+                                                              const uint64_t *__restrict__ counts)
+{
+    const uint32_t n = (uint32_t)counts[0];
+    if (n == 0) return;
+    const uint32_t perRow = collect_pieces(pitch);
+    const uint32_t total = index[n - 1u].reserved + (pitch ? perRow : collect_pieces(index[n - 1u].bytes));
+    for (uint32_t p = blockIdx.x; p < total; p += gridDim.x) {
+        uint32_t ev = 0;
+        if (pitch) {
+            ev = p / perRow;
+        } else {
+            uint32_t hi = n;                                // the last event whose first piece is <= p
+            while (hi - ev > 1u) {
+                const uint32_t mid = (ev + hi) >> 1;
+                if (index[mid].reserved <= p) ev = mid;
+                else hi = mid;
+            }
+        }
+        const uint64_t dstOff = index[ev].outOffset;
+        const uint32_t bytes = index[ev].bytes;
+        const uint8_t *src = arena + completed[ev].arenaOffset;
+        uint8_t *dst = out + dstOff;
+        const uint64_t extent = pitch ? pitch : bytes;
+        const uint64_t cp = bytes < extent ? bytes : extent;                  // event bytes in the extent
+        const uint64_t whole = cp & ~15ull, zeroFrom = (cp + 15ull) & ~15ull;
+        const uint64_t base = (uint64_t)(p - index[ev].reserved) * kCopyPiece;
+        u32x4 x[kCopyU];
+#pragma unroll
+        for (int u = 0; u < kCopyU; u++) {
+            const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
+            x[u] = (i + 16 <= whole) ? collect_ld16(src + i) : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int u = 0; u < kCopyU; u++) {
+            const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
+            if (i + 16 <= whole || (i >= zeroFrom && i < extent)) st16_nt(dst + i, x[u]);
+        }
+        // the chunk the event ends in: its bytes one by one, and in a row zeros up to the chunk's end
+        if (whole < cp && whole >= base && whole - base < kCopyPiece && threadIdx.x < 16u) {
+            const uint64_t b = whole + threadIdx.x;
+            if (b < cp) st1(dst + b, ld1(src + b));
+            else if (pitch) st1(dst + b, (uint8_t)0);
+        }
+    }
+}
+
+}  // namespace e2sar_amd

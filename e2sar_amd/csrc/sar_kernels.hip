@@ -15,7 +15,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_order, reas_upkeep, route), all
+// reas_classify, reas_store, reas_fused, reas_split, reas_order, reas_upkeep, reas_collect, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -31,6 +31,7 @@
 #include "reas_split.hpp"
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
+#include "reas_collect.hpp"
 #include "route.hpp"
 #include "wire.hpp"
 
@@ -244,6 +245,25 @@ hipError_t launch_relay_plan(const ReasDev &R, uint32_t first, uint32_t maxEvent
 {
     hipLaunchKernelGGL(relay_plan_kernel, dim3(1), dim3(kBlock), 0, stream, R, first, maxEvents, maxPld, lbTick,
                        entropyBase, d_events, d_counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint8_t *out, uint64_t outBytes,
+                          uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index, uint64_t *d_counts,
+                          hipStream_t stream)
+{
+    hipLaunchKernelGGL(collect_plan_kernel, dim3(1), dim3(kBlock), 0, stream, R, first, maxEvents, outBytes, pitch, align,
+                       d_index, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || outBytes == 0) return e;                  // no room: the plan wrote n = 0
+    // The copy's grid, from bounds only: n events of B bytes in all are at most B / piece + n
+    // pieces; B is at most outBytes, and at most what the arena holds (ragged) or the rows of
+    // the most events there can be.  collect_copy_kernel strides over any piece beyond it.
+    const uint32_t most = std::min(maxEvents, R.queueCapacity);
+    const uint64_t bound = pitch ? (uint64_t)most * pitch : R.arenaBytes;
+    const uint64_t grid = (std::min(outBytes, bound) + kCopyPiece - 1) / kCopyPiece + most;
+    hipLaunchKernelGGL(collect_copy_kernel, dim3((uint32_t)std::min<uint64_t>(grid, 0x7FFFFFFFull)), dim3(kBlock), 0, stream,
+                       R.arena, R.completed + std::min(first, R.queueCapacity), out, pitch, d_index, d_counts);
     return hipGetLastError();
 }
 

@@ -212,6 +212,12 @@ hipError_t launch_segment(const e2sar_hip_seg_event *d_events, uint32_t nEvents,
 hipError_t launch_relay_plan(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint32_t maxPld,
                              uint64_t lbTick, uint32_t entropyBase, e2sar_hip_seg_event *d_events,
                              uint32_t *d_counts, hipStream_t stream);
+// Completed records [first, ...) packed into out (pitch 0: ragged at `align`, else rows of
+// `pitch` bytes): the plan launch writes index / counts, the copy launch moves the bytes on
+// a grid sized from outBytes, maxEvents and the reassembler's capacities alone
+hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint8_t *out, uint64_t outBytes,
+                          uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index, uint64_t *d_counts,
+                          hipStream_t stream);
 hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t stride,
                              const uint32_t *lens, uint32_t n, uint64_t now, hipStream_t stream);
 // XCD-matched groups of a planned batch (seg_kernel's stripes) and the fused reassembly over them

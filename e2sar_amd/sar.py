@@ -221,6 +221,20 @@ class DeviceSegmenter:
 
 
 SEG_EVENT_BYTES = 40       # sizeof(e2sar_hip_seg_event)
+# e2sar_hip_collect_rec: one event DeviceReassembler.collect delivered, and where in `out`
+COLLECT_REC = np.dtype([("eventNum", "<u8"), ("outOffset", "<u8"), ("bytes", "<u4"), ("dataId", "<u2"),
+                        ("flags", "<u2"), ("numFragments", "<u4"), ("reserved", "<u4")])
+COLLECT_REC_BYTES = COLLECT_REC.itemsize
+assert COLLECT_REC_BYTES == 32
+
+
+def parse_collect(index: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
+    """The rows DeviceReassembler.collect wrote, on the host: waits for the device, copies
+    the index and the counts, and returns a COLLECT_REC array of the n taken events."""
+    torch.cuda.synchronize(index.device)
+    n = int(counts[0].item())
+    raw = index[: n * COLLECT_REC_BYTES].cpu().numpy().tobytes()
+    return np.frombuffer(raw, COLLECT_REC).copy()
 
 
 class DeviceReassembler:
@@ -297,6 +311,40 @@ class DeviceReassembler:
         check(lib().e2sar_hip_relay_plan(
             self._h, first_record, max_events, max_pld, int(lb_tick), entropy_base & 0xFFFF,
             C.c_void_p(events.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+
+    def collect(self, out: torch.Tensor, index: torch.Tensor, counts: torch.Tensor, first_record: int = 0,
+                max_events: Optional[int] = None, pitch: int = 0, align: int = 256,
+                stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Completed records [first_record, ...) packed into `out` (uint8 device tensor) on
+        the device, no host round trip (e2sar_hip_reas_collect): ragged at `align` when pitch
+        is 0, else rows of `pitch` bytes, zero-filled, so that out[: n * pitch] is an
+        [n, pitch] tensor.  `index`: uint8 device tensor of max_events * COLLECT_REC_BYTES
+        (max_events defaults to what it holds); `counts`: int64 device tensor, at least 4
+        entries: n, bytes of `out` spanned, records left, event bytes copied.  The records
+        stay queued; parse_collect reads the result back."""
+        if out.dtype != torch.uint8 or index.dtype != torch.uint8 or counts.dtype != torch.int64:
+            raise ValueError("out and index are uint8 tensors, counts is int64")
+        if max_events is None:
+            max_events = index.numel() // COLLECT_REC_BYTES
+        if index.numel() < max_events * COLLECT_REC_BYTES or counts.numel() < 4:
+            raise ValueError("collect buffers too small")
+        check(lib().e2sar_hip_reas_collect(
+            self._h, first_record, max_events, C.c_void_p(out.data_ptr()), out.numel(), pitch, align,
+            C.c_void_p(index.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+
+    def collect_rows(self, max_events: int, pitch: int, first_record: int = 0,
+                     stream: Optional[torch.cuda.Stream] = None):
+        """collect() in row mode into new tensors: -> (rows [max_events, pitch] uint8, index,
+        counts).  Row i < counts[0] is event i, cut or zero-filled to `pitch`; no host
+        synchronisation happens here."""
+        if pitch <= 0 or max_events <= 0:
+            raise ValueError("collect_rows needs a pitch and a row count")
+        dev = self.ctx.torch_device
+        rows = torch.empty((max_events, pitch), dtype=torch.uint8, device=dev)
+        index = torch.empty(max_events * COLLECT_REC_BYTES, dtype=torch.uint8, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        self.collect(rows.view(-1), index, counts, first_record, max_events, pitch, stream=stream)
+        return rows, index, counts
 
     # ---- split form: classify (headers, table) then scatter (bytes), for pipelining ----
     @staticmethod

@@ -333,6 +333,51 @@ int e2sar_hip_reas_compact(e2sar_hip_reas *r, void *stream);
 int e2sar_hip_reas_reset_stats(e2sar_hip_reas *r, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* device-side delivery: completed events leave the reassembler without the host.  The  */
+/* batch form of getEvent's out-params (e2sarDPReassembler.cpp:626-641) with the bytes  */
+/* staying in HBM: it replaces the poll -> host span table -> e2sar_hip_copy_spans      */
+/* round trip for a consumer that runs on the same GPU.                                 */
+
+/* One taken event: where its bytes sit in d_out.  32 bytes. */
+typedef struct e2sar_hip_collect_rec {
+    uint64_t eventNum;
+    uint64_t outOffset;     /* byte offset of the event in d_out */
+    uint32_t bytes;         /* the event's full length, also when truncated */
+    uint16_t dataId;
+    uint16_t flags;         /* E2SAR_HIP_COLLECT_* */
+    uint32_t numFragments;
+    uint32_t reserved;      /* the library's (the event's first 8-KiB copy piece); callers do not read it */
+} e2sar_hip_collect_rec;
+/* row mode: the event is longer than the pitch, its row holds the first `pitch` bytes */
+#define E2SAR_HIP_COLLECT_TRUNCATED 1u
+
+/* Pack completed records [firstRecord, firstRecord + avail) -- avail = min(records        */
+/* completed, queueCapacity) - firstRecord, 0 if that is negative: the cursor rule of      */
+/* e2sar_hip_relay_plan -- into d_out (device, outBytes bytes, 256-byte aligned), in        */
+/* record order, and describe them in d_index[0, n) (device, maxEvents entries).          */
+/*   pitch == 0, ragged: event i at the sum over j < i of bytes_j rounded up to `align`   */
+/* (a power of two in [16, 4096]; 0 = 256).  Taken: the longest prefix of the records     */
+/* with i < maxEvents whose every event ends inside outBytes; nothing after the first     */
+/* event that does not fit is taken.  Only the events' own bytes are written: the padding */
+/* between events and everything after the last keep what they held.                       */
+/*   pitch > 0 (a multiple of 16), rows: n = min(avail, maxEvents, outBytes / pitch);      */
+/* event i at i * pitch, min(bytes, pitch) bytes copied, the rest of the row zeros, flags */
+/* TRUNCATED where bytes > pitch; rows >= n keep what they held.  `align` is ignored.  A   */
+/* d_out of n rows is a [n, pitch] byte tensor.                                             */
+/*   d_counts (device, 4 entries): [0] = n; [1] = bytes of d_out spanned (the last        */
+/* event's offset + its length rounded up to `align`; n * pitch; 0 when n == 0); [2] =     */
+/* avail - n, the records left for a call with firstRecord + n; [3] = event bytes copied. */
+/* outBytes == 0 is legal (n = 0).  All offsets are 64-bit.                                 */
+/*   The records stay queued: a later poll returns them, recycle discards them.  The      */
+/* caller orders the call after the reassembly launches whose events it wants (the same  */
+/* stream, or an event).  The bytes in d_out are a copy: recycle or compact may follow as */
+/* soon as the collect has run on the stream.  Two kernel launches, no allocation, no      */
+/* memset node, no wait: the call may be captured into a HIP graph.  Asynchronous.        */
+int e2sar_hip_reas_collect(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t maxEvents,
+                           uint8_t *d_out, uint64_t outBytes, uint32_t pitch, uint32_t align,
+                           e2sar_hip_collect_rec *d_index, uint64_t *d_counts, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* relay (BASELINE config 5: receive -> reassemble -> segment -> send on one GPU): the    */
 /* events a reassembler completed are segmented again without a host round trip.  The  */
 /* Segmenter's per-event rules (numbering, dataId, entropy, LB tick: cpp:707-728,      */
