@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void relay_plan_kernel(ReasDev R, uint32_t 
         const uint32_t i = b0 + threadIdx.x;
         e2sar_hip_event_rec rec{};
         if (i < n) rec = R.completed[first + i];
-        const uint32_t np = (i < n) ? (rec.bytes + maxPld - 1u) / maxPld : 0u;
+        const uint32_t np = (i < n) ? rec.bytes / maxPld + (rec.bytes % maxPld != 0u) : 0u;
         uint32_t inc = np;                                   // inclusive scan in the wave
 #pragma unroll
         for (uint32_t o = 1; o < 64; o <<= 1) {

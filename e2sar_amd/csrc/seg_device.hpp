@@ -94,7 +94,8 @@ constexpr int kSegBlock = 256;       // seg_kernel threads per workgroup (128 / 
 // profiles/round4/ab/seg_occupancy.log)
 constexpr uint32_t kSeg4PerCU = 6;
 // One round of a segmentation block: index-space chunks [j0, j0 + SB*U) of event ev,
-// bounded by jEnd (the event's chunk count, or the end of a local chained range).
+// bounded by jEnd (the event's chunk count, or the end of a local chained range).  `out` and
+// outR address chunk outJ0, so every store offset is 16 * (j - outJ0), below 2^32.
 struct SegEv {
     SegHdr h;
     const uint8_t *data;
@@ -112,7 +113,7 @@ __device__ __forceinline__ SegEv seg_ev(const e2sar_hip_seg_event &ev, int lbVer
     E.data = ev.data;
     E.pktBase = ev.pktBase;
     E.bytes = ev.bytes;
-    E.npk = (ev.bytes + maxPld - 1u) / maxPld;
+    E.npk = ev.bytes / maxPld + (ev.bytes % maxPld != 0u);     // bytes + maxPld - 1 wraps near 4 GiB
     E.spc = stride >> 4;
     E.maxPld = maxPld;
     E.rspc = 1.0f / (float)E.spc;
@@ -206,7 +207,7 @@ __device__ __forceinline__ void seg_round(const SegEv &E, uint8_t *__restrict__ 
         // plain stores: the batch stays in the Infinity Cache for the reassembly that reads it
         // next (nt stores: reas_kernel 97.8 vs 74 us, round 3)
         if (HO) st16_sc1(outR, 16u * (jj[u] - outJ0), o);
-        else st16(out + 16u * jj[u], o);
+        else st16(out + 16u * (jj[u] - outJ0), o);
     }
 }
 
@@ -227,8 +228,10 @@ __device__ __forceinline__ void seg_block(const e2sar_hip_seg_event *__restrict_
     const uint32_t j0 = bx * (uint32_t)(SB * U);
     if (j0 >= nch) return;
 
-    uint8_t *const out = pkts + (uint64_t)ev.pktBase * stride;
-    const __amdgpu_buffer_rsrc_t outR = brsrc(out + 16ull * j0);        // HO stores only
+    // the block's first chunk: an event of more than 2^28 chunks (4 GiB of slots) puts 16 * j
+    // past 32 bits, so the 64-bit part of the address is added here, once per block
+    uint8_t *const out = pkts + (uint64_t)ev.pktBase * stride + 16ull * j0;
+    const __amdgpu_buffer_rsrc_t outR = brsrc(out);                     // HO stores only
     const uint8_t *const safe = reinterpret_cast<const uint8_t *>(events + e);   // >= 16 valid bytes
     seg_round<U, HO, SB>(E, out, outR, j0, safe, lens, j0, nch);
     if (HO) {

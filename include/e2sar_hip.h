@@ -142,7 +142,9 @@ int e2sar_hip_seg_plan(e2sar_hip_seg_event *events, uint32_t nEvents, size_t max
 
 /* Segment nEvents events (descriptor table `d_events` already on the device) into
  * datagrams [16-byte LB][20-byte RE][payload] at d_packets + p*stride, p = pktBase+k.
- * d_lens[p] (optional) receives the datagram length 36 + payload.  lbHdrVersion 3
+ * d_lens[p] (optional) receives the datagram length 36 + payload.  Padding: the bytes from
+ * the datagram's end to the end of its last 16-byte chunk are zero, and the rest of the slot
+ * (stride: any multiple of 16 that holds 36 + maxPldLen) is not written.  lbHdrVersion 3
  * selects LBHdrV3, any other value LBHdrV2 (e2sarHeaders.hpp:287-297).
  * maxPacketsPerEvent: an upper bound (from seg_plan).  eventsDwordAligned is a hint kept
  * for ABI compatibility: the kernel takes its 16-byte dword-aligned fast path for every
