@@ -40,6 +40,35 @@ class SegEvent(C.Structure):
     ]
 
 
+class SegSource(C.Structure):
+    """e2sar_hip_seg_source: where the events of e2sar_hip_seg_emit lie (device addresses)."""
+    _fields_ = [
+        ("d_data", C.c_uint64),
+        ("dataBytes", C.c_uint64),
+        ("d_bytes", C.c_uint64),
+        ("d_count", C.c_uint64),
+        ("d_offsets", C.c_uint64),
+        ("pitch", C.c_uint32),
+        ("maxEventBytes", C.c_uint32),
+    ]
+
+
+class SegNumbering(C.Structure):
+    """e2sar_hip_seg_numbering: the per-event rules e2sar_hip_seg_emit applies on the device."""
+    _fields_ = [
+        ("d_eventNums", C.c_uint64),
+        ("eventNumBase", C.c_uint64),
+        ("lbTickBase", C.c_uint64),
+        ("lbTickStep", C.c_uint64),
+        ("dataId", C.c_uint16),
+        ("entropyBase", C.c_uint16),
+        ("flags", C.c_uint32),
+    ]
+
+
+SEG_TICKS_AS_EVENTNUM = 1     # SegNumbering.flags: RE eventNum = the event's lbTick
+
+
 class CopySpan(C.Structure):
     _fields_ = [
         ("src", C.c_uint64),
@@ -134,6 +163,7 @@ class ReasStats(C.Structure):
 
 
 assert C.sizeof(SegEvent) == 40
+assert C.sizeof(SegSource) == 48 and C.sizeof(SegNumbering) == 40
 assert C.sizeof(EventRec) == 32
 assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
@@ -181,6 +211,7 @@ SIGNATURES = {
     "e2sar_hip_segment_batch": (i, [vp, vp, u32, u32, i, u32, i, vp, u32, vp, vp]),
     "e2sar_hip_segment_batch_dev": (i, [vp, vp, vp, u32, u32, i, u32, vp, u32, vp, vp]),
     "e2sar_hip_segment_batch_recycle": (i, [vp, vp, u32, u32, i, u32, i, vp, u32, vp, vp, i, vp]),
+    "e2sar_hip_seg_emit": (i, [vp, C.POINTER(SegSource), C.POINTER(SegNumbering), u32, i, u32, vp, u32, u32, vp, vp, vp, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),
     "e2sar_hip_reas_collect": (i, [vp, u32, u32, vp, u64, u32, u32, vp, vp, vp]),
     "e2sar_hip_reas_create": (i, [vp, C.POINTER(ReasConfig), C.POINTER(vp)]),

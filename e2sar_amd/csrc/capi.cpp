@@ -590,6 +590,33 @@ int e2sar_hip_segment_batch_dev(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d
                    d_lens, stream);
 }
 
+int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src, const e2sar_hip_seg_numbering *num,
+                       uint32_t maxEvents, int lbHdrVersion, uint32_t maxPldLen, uint8_t *d_packets, uint32_t stride,
+                       uint32_t maxPackets, uint32_t *d_lens, e2sar_hip_seg_event *d_events, uint32_t *d_counts,
+                       void *stream)
+{
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (maxEvents == 0) return E2SAR_HIP_OK;
+    if (!src || !num) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL source or numbering");
+    if (!src->d_data || !src->d_bytes || !d_packets || !d_events || !d_counts)
+        return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if ((src->pitch != 0) == (src->d_offsets != nullptr))
+        return fail(E2SAR_HIP_ERR_PARAMETER, "give a pitch (rows) or d_offsets (ragged), not both");
+    if (num->flags & ~E2SAR_HIP_SEG_TICKS_AS_EVENTNUM) return fail(E2SAR_HIP_ERR_PARAMETER, "unknown numbering flags");
+    if (int rc = check_seg_layout(maxPldLen, stride, d_packets)) return rc;
+    if (int rc = check_packets(d_packets, stride, maxPackets)) return rc;
+    const uint32_t U = seg_emit_u(src->pitch ? src->pitch : src->maxEventBytes, maxPldLen, stride);
+    if (seg_emit_grid(maxEvents, maxPackets, stride, U) > 0x7FFFFFFFull)
+        return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "launch too large (units of maxPackets slots + maxEvents)");
+    const EmitSrc S{src->d_data, src->dataBytes, src->d_bytes, src->d_offsets, src->d_count, src->pitch};
+    const EmitNum N{num->d_eventNums, num->eventNumBase, num->lbTickBase, num->lbTickStep, num->entropyBase, num->dataId,
+                    (num->flags & E2SAR_HIP_SEG_TICKS_AS_EVENTNUM) ? 1u : 0u};
+    return ctx_call(ctx, stream, "seg_emit launch", [&](hipStream_t s) {
+        return launch_seg_emit(S, N, maxEvents, lbHdrVersion, maxPldLen, d_packets, stride, maxPackets, d_lens, d_events,
+                               d_counts, U, s);
+    });
+}
+
 /* ---------------- reassembly ---------------- */
 
 int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, e2sar_hip_reas **out)

@@ -163,6 +163,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
     return v;
 }
 
+// The same sum by shuffles, for any integer width (the plan kernels' 64-bit scans); `lane`
+// is the caller's lane index.  Whole wave active.
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan_shfl(T v, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(v, o);
+        if (lane >= o) v += y;
+    }
+    return v;
+}
+
 // i / d from d's float reciprocal rd = 1.0f / d and a +-1 correction: exact while the
 // quotient is below 2^22 (the estimate is then off by less than one).  The copy kernels
 // turn a chunk index into (datagram, chunk within its slot) with it.

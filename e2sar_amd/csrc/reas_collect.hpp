@@ -24,17 +24,6 @@ __host__ __device__ constexpr uint32_t collect_pieces(uint64_t extent)
 // cache-allocating loads is in DESIGN.md 4.8).
 __device__ __forceinline__ u32x4 collect_ld16(const uint8_t *p) { return ld16_nt(p); }
 
-template <typename T>
-__device__ __forceinline__ T wave_incl_scan_shfl(T v, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-        const T y = __shfl_up(v, o);
-        if (lane >= o) v += y;
-    }
-    return v;
-}
-
 // One workgroup, 256 records per step (relay_plan_kernel's shape).  Per step: a block-wide
 // scan of the padded extents on top of a 64-bit carry gives every record its offset; the
 // capacity cut is the first record whose end would pass outBytes, and nothing after it is

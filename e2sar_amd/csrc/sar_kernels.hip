@@ -2,6 +2,9 @@
 //
 //   seg_kernel      : event batch -> datagram batch   (replaces _send's fragment loop,
 //                     e2sarDPSegmenter.cpp:702-770)
+//   emit_plan + seg_flat : the same for events whose count, lengths and offsets live in
+//                     device memory, with the per-event rules in front of the loop
+//                     (cpp:707-728, 901-948) applied on the device
 //   reas_classify   : datagram batch -> per-packet destination + event table updates
 //                     (replaces the recv body's parse/validate/find-or-create/complete,
 //                     e2sarDPReassembler.cpp:335-427)
@@ -15,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_order, reas_upkeep, reas_collect, route), all
+// reas_classify, reas_store, reas_fused, reas_split, reas_order, reas_upkeep, reas_collect, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -32,6 +35,7 @@
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
 #include "reas_collect.hpp"
+#include "seg_emit.hpp"
 #include "route.hpp"
 #include "wire.hpp"
 
@@ -264,6 +268,42 @@ hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, 
     const uint64_t grid = (std::min(outBytes, bound) + kCopyPiece - 1) / kCopyPiece + most;
     hipLaunchKernelGGL(collect_copy_kernel, dim3((uint32_t)std::min<uint64_t>(grid, 0x7FFFFFFFull)), dim3(kBlock), 0, stream,
                        R.arena, R.completed + std::min(first, R.queueCapacity), out, pitch, d_index, d_counts);
+    return hipGetLastError();
+}
+
+uint32_t seg_emit_u(uint64_t boundBytes, uint32_t maxPld, uint32_t stride)
+{
+    if (boundBytes == 0 || maxPld == 0) return 4u;
+    const uint64_t chunks = (boundBytes + maxPld - 1) / maxPld * (stride >> 4);
+    return chunks <= (1u << 18) ? 2u : 4u;                    // seg_geom's rule
+}
+
+uint64_t seg_emit_grid(uint32_t maxEvents, uint32_t maxPackets, uint32_t stride, uint32_t U)
+{
+    const uint64_t chunks = (uint64_t)maxPackets * (stride >> 4);
+    if (chunks > 0xFFFFFFFFull || (stride >> 4) == 0) return 0;
+    const uint64_t unitChunks = (uint64_t)kSegBlock * U;
+    return (chunks + unitChunks - 1) / unitChunks + maxEvents;
+}
+
+hipError_t launch_seg_emit(const EmitSrc &S, const EmitNum &N, uint32_t maxEvents, int lbVersion, uint32_t maxPld,
+                           uint8_t *pkts, uint32_t stride, uint32_t maxPackets, uint32_t *lens,
+                           e2sar_hip_seg_event *d_events, uint32_t *d_counts, uint32_t U, hipStream_t stream)
+{
+    const uint64_t grid = seg_emit_grid(maxEvents, maxPackets, stride, U);
+    if (maxEvents == 0 || maxPld == 0 || grid == 0 || grid > 0x7FFFFFFFull || (U != 2u && U != 4u)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(emit_plan_kernel, dim3(1), dim3(kBlock), 0, stream, S, N, maxEvents, maxPld, maxPackets, stride >> 4,
+                       (uint32_t)kSegBlock * U, d_events, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // n events of C chunks in all are at most C / unit + n units: the grid never undercounts
+    if (U == 2)
+        hipLaunchKernelGGL((seg_flat_kernel<2>), dim3((uint32_t)grid), dim3(kSegBlock), 0, stream, d_events, d_counts,
+                           lbVersion, maxPld, pkts, stride, lens);
+    else
+        hipLaunchKernelGGL((seg_flat_kernel<4>), dim3((uint32_t)grid), dim3(kSegBlock),
+                           occupancy_lds(seg_flat_kernel<4>, kSeg4PerCU), stream, d_events, d_counts, lbVersion, maxPld, pkts,
+                           stride, lens);
     return hipGetLastError();
 }
 

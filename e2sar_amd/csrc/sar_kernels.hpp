@@ -212,6 +212,32 @@ hipError_t launch_segment(const e2sar_hip_seg_event *d_events, uint32_t nEvents,
 hipError_t launch_relay_plan(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint32_t maxPld,
                              uint64_t lbTick, uint32_t entropyBase, e2sar_hip_seg_event *d_events,
                              uint32_t *d_counts, hipStream_t stream);
+// Device-side production (e2sar_hip_seg_emit): where the events lie and how they are
+// numbered, passed by value to emit_plan_kernel.  Event i of the source: `bytes[i]` bytes at
+// data + i * pitch (pitch > 0) or at data + offsets[i]; their count is min(*count, maxEvents)
+// (count may be NULL).  Numbering: e2sar_hip_seg_numbering's rules.
+struct EmitSrc {
+    const uint8_t *data;
+    uint64_t dataBytes;
+    const uint32_t *bytes;
+    const uint64_t *offsets;
+    const uint32_t *count;
+    uint32_t pitch;
+};
+struct EmitNum {
+    const uint64_t *eventNums;
+    uint64_t eventNumBase, lbTickBase, lbTickStep;
+    uint32_t entropyBase, dataId, ticksAsEventNum;
+};
+// 16-byte chunks per thread of the flat launch, by seg_geom's rule, for events of at most
+// boundBytes bytes (0 = unknown: 4); and the launch's grid, from bounds alone: every unit
+// maxPackets slots can hold plus one per event (0 when a slot chunk index would pass 32 bits)
+uint32_t seg_emit_u(uint64_t boundBytes, uint32_t maxPld, uint32_t stride);
+uint64_t seg_emit_grid(uint32_t maxEvents, uint32_t maxPackets, uint32_t stride, uint32_t U);
+// emit_plan_kernel, then seg_flat_kernel<U> over seg_emit_grid workgroups (at most 2^31 - 1)
+hipError_t launch_seg_emit(const EmitSrc &S, const EmitNum &N, uint32_t maxEvents, int lbVersion, uint32_t maxPld,
+                           uint8_t *pkts, uint32_t stride, uint32_t maxPackets, uint32_t *lens,
+                           e2sar_hip_seg_event *d_events, uint32_t *d_counts, uint32_t U, hipStream_t stream);
 // Completed records [first, ...) packed into out (pitch 0: ragged at `align`, else rows of
 // `pitch` bytes): the plan launch writes index / counts, the copy launch moves the bytes on
 // a grid sized from outBytes, maxEvents and the reassembler's capacities alone

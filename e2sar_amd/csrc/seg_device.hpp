@@ -211,16 +211,14 @@ __device__ __forceinline__ void seg_round(const SegEv &E, uint8_t *__restrict__ 
     }
 }
 
+// Unit bx (SB * U consecutive chunks) of event e: what a segmentation workgroup does once it
+// knows its place, whether that came from an event-major grid (seg_block) or from a search
+// over a unit prefix (seg_flat_kernel, seg_emit.hpp).
 template <int U, bool HO, int SB = kBlock>
-__device__ __forceinline__ void seg_block(const e2sar_hip_seg_event *__restrict__ events, uint32_t blocksPerEvent,
-                                          int lbVersion, uint32_t maxPld, uint8_t *__restrict__ pkts, uint32_t stride,
-                                          uint32_t *__restrict__ lens, const uint32_t *__restrict__ dCount,
-                                          uint32_t blk, uint32_t tileG, uint32_t *__restrict__ tiles)
+__device__ __forceinline__ void seg_unit(const e2sar_hip_seg_event *__restrict__ events, uint32_t e, uint32_t bx,
+                                         int lbVersion, uint32_t maxPld, uint8_t *__restrict__ pkts, uint32_t stride,
+                                         uint32_t *__restrict__ lens, uint32_t tileG, uint32_t *__restrict__ tiles)
 {
-    TRACE_AT(1, 0, trace_now());
-    const uint32_t e = blk / blocksPerEvent;
-    const uint32_t bx = blk - e * blocksPerEvent;
-    if (dCount && e >= *dCount) return;
     const e2sar_hip_seg_event ev = events[e];
     const SegEv E = seg_ev(ev, lbVersion, maxPld, stride);
     const uint32_t spc = E.spc;
@@ -258,6 +256,19 @@ __device__ __forceinline__ void seg_block(const e2sar_hip_seg_event *__restrict_
     TRACE_AT(1, 2, trace_hwid());
     TRACE_AT(1, 3, trace_now());
 #endif
+}
+
+template <int U, bool HO, int SB = kBlock>
+__device__ __forceinline__ void seg_block(const e2sar_hip_seg_event *__restrict__ events, uint32_t blocksPerEvent,
+                                          int lbVersion, uint32_t maxPld, uint8_t *__restrict__ pkts, uint32_t stride,
+                                          uint32_t *__restrict__ lens, const uint32_t *__restrict__ dCount,
+                                          uint32_t blk, uint32_t tileG, uint32_t *__restrict__ tiles)
+{
+    TRACE_AT(1, 0, trace_now());
+    const uint32_t e = blk / blocksPerEvent;
+    const uint32_t bx = blk - e * blocksPerEvent;
+    if (dCount && e >= *dCount) return;
+    seg_unit<U, HO, SB>(events, e, bx, lbVersion, maxPld, pkts, stride, lens, tileG, tiles);
 }
 
 // stripe > 0 (XCD stripes): the dispatcher hands workgroup b to XCD b mod 8 (round robin,

@@ -219,8 +219,86 @@ class DeviceSegmenter:
             self.stride, C.c_void_p(lens.data_ptr() if lens is not None else 0),
             C.c_void_p(_stream_handle(stream))))
 
+    def emit(self, data: torch.Tensor, lengths: torch.Tensor, packets: torch.Tensor, lens: Optional[torch.Tensor],
+             events: torch.Tensor, counts: torch.Tensor, *, offsets: Optional[torch.Tensor] = None, pitch: int = 0,
+             count: Optional[torch.Tensor] = None, event_nums: Optional[torch.Tensor] = None,
+             event_num_base: int = 0, lb_tick_base: int = 0, lb_tick_step: int = 0, data_id: int = 0,
+             entropy_base: int = 0, ticks_as_event_num: bool = False, max_events: Optional[int] = None,
+             max_event_bytes: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Plan and segment events whose count, lengths and offsets live on the device
+        (e2sar_hip_seg_emit): two launches, no allocation, no wait, capturable.
+
+        `data`: uint8 device tensor the events lie in; event i has lengths[i] bytes (int32
+        device tensor, read as uint32) at i * pitch (rows) or at offsets[i] (int64 device
+        tensor, ragged) -- give one of the two.  `count`: a one-element int32 device tensor
+        (None: every entry of `lengths`).  Numbering of event i: RE eventNum event_nums[i]
+        (int64 device tensor) or event_num_base + i, lbTick lb_tick_base + i * lb_tick_step,
+        entropy entropy_base + i; ticks_as_event_num puts the lbTick into the RE eventNum.
+        `packets` / `lens` bound the datagrams (packets.numel() // stride slots); `events`:
+        uint8 device tensor of max_events * SEG_EVENT_BYTES; `counts`: int32 device tensor of
+        at least 8 entries: taken, datagrams, events left, why the prefix ended (0 all taken,
+        1 packet capacity, 2 event outside `data`).  parse_emit reads the result back."""
+        if data.dtype != torch.uint8 or packets.dtype != torch.uint8 or events.dtype != torch.uint8:
+            raise ValueError("data, packets and events are uint8 tensors")
+        if lengths.dtype != torch.int32 or counts.dtype != torch.int32 or (count is not None and count.dtype != torch.int32):
+            raise ValueError("lengths, counts and count are int32 tensors")
+        if (offsets is not None and offsets.dtype != torch.int64) or (event_nums is not None and event_nums.dtype != torch.int64):
+            raise ValueError("offsets and event_nums are int64 tensors")
+        if max_events is None:
+            max_events = lengths.numel()
+        max_packets = packets.numel() // self.stride
+        if lens is not None:
+            max_packets = min(max_packets, lens.numel())
+        if (lengths.numel() < max_events or events.numel() < max_events * SEG_EVENT_BYTES or counts.numel() < 8
+                or (offsets is not None and offsets.numel() < max_events)
+                or (event_nums is not None and event_nums.numel() < max_events)):
+            raise ValueError("emit buffers too small for max_events")
+        ptr = lambda t: t.data_ptr() if t is not None else 0
+        src = _capi.SegSource(ptr(data), data.numel(), ptr(lengths), ptr(count), ptr(offsets), int(pitch),
+                              min(int(max_event_bytes), 0xFFFFFFFF))
+        num = _capi.SegNumbering(ptr(event_nums), int(event_num_base) & (2**64 - 1), int(lb_tick_base) & (2**64 - 1),
+                                 int(lb_tick_step) & (2**64 - 1), int(data_id) & 0xFFFF, int(entropy_base) & 0xFFFF,
+                                 _capi.SEG_TICKS_AS_EVENTNUM if ticks_as_event_num else 0)
+        check(lib().e2sar_hip_seg_emit(
+            self.ctx.handle, C.byref(src), C.byref(num), max_events, self.lb_hdr_version, self.max_pld,
+            C.c_void_p(packets.data_ptr()), self.stride, max_packets, C.c_void_p(ptr(lens)),
+            C.c_void_p(events.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+
+    def emit_rows(self, rows: torch.Tensor, lengths: torch.Tensor, count: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, **numbering):
+        """emit() of the rows of a contiguous [n, pitch] uint8 tensor into new tensors sized
+        for the bound (every row full): -> (packets, lens, events, counts).  Row i < counts[0]
+        is event i with lengths[i] bytes; no host synchronisation happens here."""
+        if rows.dim() != 2 or rows.dtype != torch.uint8 or not rows.is_contiguous():
+            raise ValueError("emit_rows needs a contiguous [n, pitch] uint8 tensor")
+        n, pitch = rows.shape
+        if n == 0 or pitch == 0:
+            raise ValueError("emit_rows needs at least one row of at least one byte")
+        dev = self.ctx.torch_device
+        packets, lens = self.alloc_packets(n * num_packets(pitch, self.max_pld))
+        events = torch.empty(n * SEG_EVENT_BYTES, dtype=torch.uint8, device=dev)
+        counts = torch.empty(8, dtype=torch.int32, device=dev)
+        self.emit(rows.view(-1), lengths, packets, lens, events, counts, pitch=pitch, count=count, max_events=n,
+                  stream=stream, **numbering)
+        return packets, lens, events, counts
+
 
 SEG_EVENT_BYTES = 40       # sizeof(e2sar_hip_seg_event)
+# e2sar_hip_seg_event, as DeviceSegmenter.emit and DeviceReassembler.relay_plan write it
+SEG_EVENT = np.dtype([("data", "<u8"), ("eventNum", "<u8"), ("lbTick", "<u8"), ("bytes", "<u4"), ("pktBase", "<u4"),
+                      ("dataId", "<u2"), ("entropy", "<u2"), ("reserved", "<u4")])
+assert SEG_EVENT.itemsize == SEG_EVENT_BYTES
+
+
+def parse_emit(events: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
+    """The descriptors DeviceSegmenter.emit wrote, on the host: waits for the device, copies
+    the table and the counts, and returns a SEG_EVENT array of the n taken events."""
+    torch.cuda.synchronize(events.device)
+    n = int(counts[0].item())
+    raw = events[: n * SEG_EVENT_BYTES].cpu().numpy().tobytes()
+    return np.frombuffer(raw, SEG_EVENT).copy()
+
+
 # e2sar_hip_collect_rec: one event DeviceReassembler.collect delivered, and where in `out`
 COLLECT_REC = np.dtype([("eventNum", "<u8"), ("outOffset", "<u8"), ("bytes", "<u4"), ("dataId", "<u2"),
                         ("flags", "<u2"), ("numFragments", "<u4"), ("reserved", "<u4")])

@@ -403,6 +403,74 @@ int e2sar_hip_segment_batch_dev(e2sar_hip_ctx *ctx, const e2sar_hip_seg_event *d
                                 uint32_t *d_lens, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* device-side production: events a kernel on the same GPU produced are segmented      */
+/* without the host knowing their count, lengths or offsets.  Replaces, for a batch,   */
+/* the _send loop (e2sarDPSegmenter.cpp:660-871) and, on the device, the Segmenter's   */
+/* per-event rules the host applies in front of it (cpp:707-728, 901-948).  The send-  */
+/* side mirror of e2sar_hip_reas_collect.                                              */
+
+/* Where the events lie.  Event i has d_bytes[i] bytes.                                 */
+/*   pitch > 0, rows: event i at d_data + i * pitch; d_offsets must be NULL.            */
+/*   pitch == 0, ragged: event i at d_data + d_offsets[i] (device u64 array).           */
+/* Available events: min(*d_count, maxEvents), or maxEvents when d_count is NULL; in    */
+/* row mode also at most dataBytes / pitch.  Any address alignment is legal (the kernel */
+/* picks its dword or byte path per event).  maxEventBytes: a hint for ragged events, an */
+/* upper bound of their lengths (0 = unknown); it selects a kernel instantiation only,  */
+/* results do not depend on it.  48 bytes.                                              */
+typedef struct e2sar_hip_seg_source {
+    const uint8_t *d_data;     /* device region the events lie in */
+    uint64_t dataBytes;        /* its size */
+    const uint32_t *d_bytes;   /* device u32[maxEvents]: event lengths */
+    const uint32_t *d_count;   /* device u32, or NULL */
+    const uint64_t *d_offsets; /* device u64[maxEvents] (ragged), or NULL (rows) */
+    uint32_t pitch;
+    uint32_t maxEventBytes;
+} e2sar_hip_seg_source;
+
+/* How the events are numbered (the host rules of cpp:707-728 and 901-948, per event i   */
+/* of the source): RE eventNum = d_eventNums[i] if that device array is given, else      */
+/* eventNumBase + i (64-bit wrap); lbTick = lbTickBase + i * lbTickStep; dataId constant; */
+/* entropy = entropyBase + i (mod 2^16), e2sar_hip_relay_plan's rule; with               */
+/* E2SAR_HIP_SEG_TICKS_AS_EVENTNUM the RE eventNum is the event's lbTick (cpp:723-724). */
+/* 40 bytes.                                                                             */
+typedef struct e2sar_hip_seg_numbering {
+    const uint64_t *d_eventNums;   /* device u64[maxEvents], or NULL */
+    uint64_t eventNumBase;
+    uint64_t lbTickBase;
+    uint64_t lbTickStep;
+    uint16_t dataId;
+    uint16_t entropyBase;
+    uint32_t flags;                /* E2SAR_HIP_SEG_* */
+} e2sar_hip_seg_numbering;
+#define E2SAR_HIP_SEG_TICKS_AS_EVENTNUM 1u
+
+/* Plan and segment the source's events in one call: two kernel launches, no allocation,  */
+/* no memset node, no wait -- the call may be captured into a HIP graph.                  */
+/*   Taken: the longest prefix of the available events in which (a) every event's bytes   */
+/* lie inside the source -- rows: bytes <= pitch; ragged: offset + bytes <= dataBytes, in */
+/* 64 bits -- and (b) all datagrams fit in maxPackets slots.  Nothing after the first     */
+/* event that fails either test is taken, even if it would fit.  No byte of an event that */
+/* was not taken is read.                                                                 */
+/*   d_counts (device, 8 entries): [0] = n taken; [1] = their datagram count; [2] =       */
+/* available - n; [3] = why the prefix ended: 0 all taken, 1 packet capacity, 2 an event  */
+/* outside its source (also: rows the count names lie past dataBytes); [4] the library's  */
+/* (the unit total the copy launch reads); [5..7] reserved.                               */
+/*   d_events[0, n) (device, maxEvents entries): the descriptors e2sar_hip_seg_plan would */
+/* produce for the same lengths (pktBase the exclusive prefix of ceil(bytes/maxPldLen), an */
+/* empty event has no datagram), except `reserved`, which is the library's.  Entries at   */
+/* or past n, and slots and d_lens entries at or past d_counts[1], keep what they held.   */
+/*   Datagram bytes, zero fill and d_lens (optional): e2sar_hip_segment_batch's contract. */
+/* Status: PARAMETER for a NULL required pointer, pitch and d_offsets both set or neither, */
+/* maxPldLen 0 or above a UDP datagram, a bad stride, unknown flags; OUT_OF_RANGE when     */
+/* maxPackets * (stride / 16) exceeds 2^32 - 1 or the launch would exceed 2^31 - 1         */
+/* workgroups.  maxEvents == 0 succeeds with nothing launched.  Asynchronous.             */
+int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src,
+                       const e2sar_hip_seg_numbering *num, uint32_t maxEvents,
+                       int lbHdrVersion, uint32_t maxPldLen,
+                       uint8_t *d_packets, uint32_t stride, uint32_t maxPackets, uint32_t *d_lens,
+                       e2sar_hip_seg_event *d_events, uint32_t *d_counts, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* multi-GPU: events are owned by rank eventNum % world.  A rank that received       */
 /* (landed) datagrams of other ranks' events routes them: this packs the batch into */
 /* per-destination spans (stable order) and reports the span sizes, ready for one   */
