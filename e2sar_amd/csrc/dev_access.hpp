@@ -1,4 +1,6 @@
-// dev_access.hpp -- vector types, shared launch constants, trace macros, memory accessors and wave helpers of the device code.
+// dev_access.hpp -- vector types, shared launch constants, trace macros and memory accessors of the device code, and
+// its wave and workgroup idioms: lane moves and reads, wave scans and min / max, the wave's LDS sync, run heads, and the
+// planners' block scan and first-failure cut.
 #pragma once
 
 #include "sar_kernels.hpp"
@@ -174,6 +176,91 @@ __device__ __forceinline__ T wave_incl_scan_shfl(T v, uint32_t lane)
         if (lane >= o) v += y;
     }
     return v;
+}
+
+// The value lane `lane` (wave-uniform) holds, as a scalar.
+__device__ __forceinline__ uint32_t readlane(uint32_t v, uint32_t lane)
+{
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
+}
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, uint32_t lane)
+{
+    return ((uint64_t)readlane((uint32_t)(v >> 32), lane) << 32) | readlane((uint32_t)v, lane);
+}
+
+// What one wave's lanes wrote to LDS is visible to all of them after this.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The last lane at or below `lane` whose bit is set in `heads` (the head of the run the lane
+// is in), or `lane` itself if there is none.
+__device__ __forceinline__ int run_head_lane(uint64_t heads, uint32_t lane)
+{
+    const uint64_t le = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
+    const uint64_t hm = heads & le;
+    return hm ? 63 - __builtin_clzll(hm) : (int)lane;
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+
+// Scans over a workgroup of NW waves, all threads active (`part`: NW words of LDS).
+// block_scan_post scans v in the wave and posts the wave's sum; after a barrier
+// block_scan_before gives the sum of the waves in front of the caller's, and of all of them
+// in `total`.  block_excl_scan is the two around their barrier: the exclusive prefix of v.
+// The caller keeps a barrier between a scan's reads of `part` and the next writes to it.
+template <typename T>
+__device__ __forceinline__ T block_scan_post(T v, T *part)
+{
+    const T inc = wave_incl_scan_shfl(v, threadIdx.x & 63u);
+    if ((threadIdx.x & 63u) == 63u) part[threadIdx.x >> 6] = inc;
+    return inc;
+}
+template <typename T, int NW>
+__device__ __forceinline__ T block_scan_before(const T *part, T &total)
+{
+    T before = total = 0;
+    for (uint32_t w = 0; w < (uint32_t)NW; w++) {
+        if (w < (threadIdx.x >> 6)) before += part[w];
+        total += part[w];
+    }
+    return before;
+}
+template <typename T, int NW>
+__device__ __forceinline__ T block_excl_scan(T v, T *part, T &total)
+{
+    const T inc = block_scan_post(v, part);
+    __syncthreads();
+    return block_scan_before<T, NW>(part, total) + inc - v;
+}
+
+// The key of the first thread of the workgroup for which `fails` holds, or all ones when
+// there is none -- the cut of the collect and emit planners.  The keys ascend with the thread
+// index (an index, or an index above a tag).  One barrier; `part` is NW words of LDS.
+template <typename K, int NW>
+__device__ __forceinline__ K block_first(bool fails, K key, K *part)
+{
+    const uint64_t miss = __ballot(fails);
+    const K first = __shfl(key, miss ? __builtin_ctzll(miss) : 0);      // the wave's first
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = miss ? first : ~(K)0;
+    __syncthreads();
+    K cut = ~(K)0;
+    for (uint32_t w = 0; w < (uint32_t)NW; w++) cut = part[w] < cut ? part[w] : cut;
+    return cut;
 }
 
 // i / d from d's float reciprocal rd = 1.0f / d and a +-1 correction: exact while the

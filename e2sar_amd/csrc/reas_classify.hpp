@@ -54,8 +54,8 @@ __device__ __forceinline__ void wave_stats(const ReasDev &R, bool live, uint32_t
     const uint64_t nder = __builtin_popcountll(__ballot(derr));
     // 64 lengths summed as 16-bit halves (each half-sum fits 32 bits, whatever the lengths)
     const uint32_t tl = live ? len : 0u;
-    const uint64_t tb = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tl & 0xFFFFu), 63) +
-                        ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tl >> 16), 63) << 16);
+    const uint64_t tb = (uint64_t)readlane(wave_incl_scan(tl & 0xFFFFu), 63) +
+                        ((uint64_t)readlane(wave_incl_scan(tl >> 16), 63) << 16);
     if ((threadIdx.x & 63u) == 0) {
         ReasShard *sh = R.shards + (shard % kShards);
         if (np) atomicAdd(&sh->totalPackets, (unsigned long long)np);
@@ -170,10 +170,7 @@ __device__ Classified classify_wave(const ReasDev &R, const RawHdr &raw, uint32_
     // pre-pass)
     const LookupResult lr = find_or_create(R, head, ev, d, blen, now);
 
-    const uint64_t H = __ballot(head);
-    const uint64_t le = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-    const uint64_t hm = H & le;
-    const int myhead = hm ? 63 - __builtin_clzll(hm) : lane;
+    const int myhead = run_head_lane(__ballot(head), (uint32_t)lane);
     const uint32_t slot = __shfl(lr.slot, myhead);
     const uint32_t sbytes = __shfl(lr.bytes, myhead);
     const uint64_t boff = shfl_u64(lr.bufOff, myhead);

@@ -35,11 +35,10 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
                                                               e2sar_hip_collect_rec *__restrict__ index,
                                                               uint64_t *__restrict__ counts)
 {
-    constexpr uint32_t kWaves = kBlock / 64;
+    constexpr int kWaves = kBlock / 64;
     __shared__ uint64_t wavePad[kWaves], waveTaken[kWaves], waveCopied[kWaves];
     __shared__ uint32_t wavePieces[kWaves], waveCut[kWaves];
     __shared__ uint32_t sAvail, sLimit;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) {
         uint32_t stored = ld_agent(&R.ctl->nCompleted);
         if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
@@ -60,33 +59,23 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
         if (active) rec = R.completed[first + i];
         const uint64_t extent = pitch ? (uint64_t)pitch : (uint64_t)rec.bytes;
         const uint64_t pad = !active ? 0ull : pitch ? (uint64_t)pitch : (((uint64_t)rec.bytes + align - 1u) & ~(uint64_t)(align - 1u));
-        const uint64_t incPad = wave_incl_scan_shfl(pad, lane);
-        if (lane == 63) wavePad[wv] = incPad;
-        __syncthreads();
-        uint64_t off = carry + incPad - pad;
-        for (uint32_t w = 0; w < wv; w++) off += wavePad[w];
+        uint64_t stepPad, stepTaken, stepCopied;
+        uint32_t stepPieces;
+        const uint64_t off = carry + block_excl_scan<uint64_t, kWaves>(pad, wavePad, stepPad);
         // rows were cut by outBytes / pitch above; a ragged event must end inside the buffer
         const bool fits = !active || pitch || off + rec.bytes <= outBytes;
-        const unsigned long long miss = __ballot(!fits);
-        if (lane == 0) waveCut[wv] = miss ? b0 + wv * 64u + (uint32_t)__builtin_ctzll(miss) : ~0u;
-        __syncthreads();
-        uint32_t cut = ~0u;
-        for (uint32_t w = 0; w < kWaves; w++) cut = waveCut[w] < cut ? waveCut[w] : cut;
+        const uint32_t cut = block_first<uint32_t, kWaves>(!fits, i, waveCut);
         const bool taken = active && i < cut;
         const uint32_t np = taken ? collect_pieces(extent) : 0u;
         const uint64_t cp = !taken ? 0ull : rec.bytes < extent ? (uint64_t)rec.bytes : extent;
-        const uint32_t incNp = wave_incl_scan_shfl(np, lane);
-        const uint64_t incTaken = wave_incl_scan_shfl(taken ? pad : 0ull, lane);
-        const uint64_t incCp = wave_incl_scan_shfl(cp, lane);
-        if (lane == 63) {
-            wavePieces[wv] = incNp;
-            waveTaken[wv] = incTaken;
-            waveCopied[wv] = incCp;
-        }
+        const uint32_t incNp = block_scan_post(np, wavePieces);      // three scans behind one barrier
+        block_scan_post(taken ? pad : (uint64_t)0, waveTaken);
+        block_scan_post(cp, waveCopied);
         __syncthreads();
+        const uint32_t before = pieces + block_scan_before<uint32_t, kWaves>(wavePieces, stepPieces);
+        block_scan_before<uint64_t, kWaves>(waveTaken, stepTaken);
+        block_scan_before<uint64_t, kWaves>(waveCopied, stepCopied);
         if (taken) {
-            uint32_t before = pieces;
-            for (uint32_t w = 0; w < wv; w++) before += wavePieces[w];
             e2sar_hip_collect_rec o;
             o.eventNum = rec.eventNum;
             o.outOffset = off;
@@ -97,11 +86,9 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
             o.reserved = before + incNp - np;
             index[i] = o;
         }
-        for (uint32_t w = 0; w < kWaves; w++) {
-            pieces += wavePieces[w];
-            carry += waveTaken[w];
-            copied += waveCopied[w];
-        }
+        pieces += stepPieces;
+        carry += stepTaken;
+        copied += stepCopied;
         if (cut != ~0u) {                                   // the same in every thread
             n = cut;
             break;

@@ -45,6 +45,86 @@ constexpr uint32_t kRoNoSlot = 0xFFFFFFFFu;
 // datagrams per lane, one workgroup per CU: 148-149 / 237 -- too few workgroups).
 constexpr int kRoKeyBlock = 1024;
 
+// The key pass's view of one datagram's header: parse_hdr, less what takes no part.
+// (Returned by value: with `foreign` handed back through a reference the kernel grew by 18
+// instructions.)
+struct RoHdr {
+    ParsedHdr h;
+    bool foreign;
+};
+__device__ __forceinline__ RoHdr ro_parse_hdr(const ReasDev &R, const RawHdr &raw, uint32_t hl, uint32_t stride, bool live)
+{
+    ParsedHdr h = parse_hdr(raw, hl, stride, live);
+    const bool foreign = h.ok && foreign_event(R, h.ev);      // another rank's event: takes no part
+    if (foreign) h = ParsedHdr{0, 0, 0, 0, 0, false, false, false};
+    // bounds against the fragment's own bufferLength, before the lookup (the reference
+    // memcpy's unchecked at cpp:391; dropped and counted here, DESIGN.md 5.3)
+    if (h.ok && (uint64_t)h.off + h.pl > h.blen) {
+        h.ok = false;
+        h.derr = true;
+    }
+    return RoHdr{h, foreign};
+}
+
+// Each head claims or finds its key's entry in the workgroup's table of NK entries (tags
+// cleared by the caller) and returns it; called by every thread of the workgroup.
+template <uint32_t NK>
+__device__ __forceinline__ uint32_t ro_wg_key(bool head, uint64_t ev, uint32_t d, unsigned long long *wgEv,
+                                              uint32_t *wgD, uint32_t *wgTag)
+{
+    uint32_t e = slot_hash(ev, d, NK - 1u);
+    bool pending = head, check = false;
+    __syncthreads();                                           // table cleared
+    while (__syncthreads_or(pending)) {
+        if (pending) {
+            if (atomicCAS(&wgTag[e], 0u, 1u) == 0u) {
+                wgEv[e] = ev;
+                wgD[e] = d;
+                pending = false;
+            } else {
+                check = true;
+            }
+        }
+        __syncthreads();                                       // claimed keys are written
+        if (check) {
+            check = false;
+            if (wgEv[e] == ev && wgD[e] == d) pending = false;
+            else e = (e + 1u) & (NK - 1u);
+        }
+    }
+    return e;
+}
+
+// Runs of consecutive positions of one key (one slot) within the wave -- they start at the
+// heads -- filed in the slot's bucket (the run of index 0 lists the slot for the walk), past
+// kRoBucket runs at their head's position in the overflow list.  k: the run's index in its key.
+__device__ __forceinline__ void ro_file_runs(const RoScratch &sc, bool ok, uint32_t slot, uint32_t k, uint32_t p,
+                                             uint32_t lane, uint32_t wave, bool waveLive)
+{
+    const uint32_t ks = ok ? slot : kRoNoSlot;
+    const uint32_t pks = lane_prev(ks, kRoNoSlot), nks = lane_next(ks, kRoNoSlot);
+    const bool rhead = ok && (lane == 0 || pks != ks);
+    const bool rtail = ok && (lane == 63 || nks != ks);
+    const uint64_t RT = __ballot(rtail);
+    if (rhead) {
+        const uint64_t below = (1ull << lane) - 1ull;
+        const uint32_t len = (uint32_t)__builtin_ctzll(RT & ~below) - lane + 1u;   // to this run's last lane
+        if (k == 0u) sc.active[atomicAdd(&sc.ctr[1], 1u)] = slot;
+        if (k < kRoBucket) {
+            sc.bucket[(size_t)slot * kRoBucket + k] = ((unsigned long long)p << 32) | len;
+        } else {
+            st16(reinterpret_cast<uint8_t *>(sc.runs + p), u32x4{slot, p, len, k});   // at its head's position
+        }
+    }
+    // which lanes of this wave hold an overflow run (every wave writes its word; a flag tells
+    // the place pass to look -- a plain store, not a counter all waves would contend on)
+    const uint64_t OV = __ballot(rhead && k >= kRoBucket);
+    if (lane == 0 && waveLive) {
+        sc.ovMask[wave] = OV;
+        if (OV) sc.ctr[0] = 1u;
+    }
+}
+
 template <int TB>
 __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__restrict__ pkts, uint32_t stride,
                                                     const uint32_t *__restrict__ lens, uint32_t n, uint64_t now,
@@ -68,15 +148,9 @@ __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__
     }
     const RawHdr raw = load_hdr(R, pkts, stride, lens, p);
     const uint32_t hl = R.withLB ? kLBREHdrLen : kREHdrLen;
-    ParsedHdr h = parse_hdr(raw, hl, stride, live);
-    const bool foreign = h.ok && foreign_event(R, h.ev);      // another rank's event: takes no part
-    if (foreign) h = ParsedHdr{0, 0, 0, 0, 0, false, false, false};
-    // bounds against the fragment's own bufferLength, before the lookup (the reference
-    // memcpy's unchecked at cpp:391; dropped and counted here, DESIGN.md 5.3)
-    if (h.ok && (uint64_t)h.off + h.pl > h.blen) {
-        h.ok = false;
-        h.derr = true;
-    }
+    const RoHdr rh = ro_parse_hdr(R, raw, hl, stride, live);
+    ParsedHdr h = rh.h;
+    const bool foreign = rh.foreign;
     // runs of equal keys: only the run head takes part.  Every head registers its key in the
     // workgroup's table itself and takes its run index there with one LDS atomic (round 6:
     // a per-wave loop that first collapsed the heads of one key took 64 passes in a wave of
@@ -85,27 +159,7 @@ __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__
     const uint64_t pev = ((uint64_t)lane_prev((uint32_t)(h.ev >> 32), 0u) << 32) | lane_prev((uint32_t)h.ev, 0u);
     const uint32_t pd = lane_prev(h.d, 0u), pok = lane_prev(h.ok ? 1u : 0u, 0u);
     const bool head = h.ok && (lane == 0 || !pok || pev != h.ev || pd != h.d);
-    // each head claims or finds its key's entry in the workgroup's table
-    uint32_t e = slot_hash(h.ev, h.d, kWgKeys - 1u);
-    bool pending = head, check = false;
-    __syncthreads();                                           // table cleared
-    while (__syncthreads_or(pending)) {
-        if (pending) {
-            if (atomicCAS(&wgTag[e], 0u, 1u) == 0u) {
-                wgEv[e] = h.ev;
-                wgD[e] = h.d;
-                pending = false;
-            } else {
-                check = true;
-            }
-        }
-        __syncthreads();                                       // claimed keys are written
-        if (check) {
-            check = false;
-            if (wgEv[e] == h.ev && wgD[e] == h.d) pending = false;
-            else e = (e + 1u) & (kWgKeys - 1u);
-        }
-    }
+    const uint32_t e = ro_wg_key<kWgKeys>(head, h.ev, h.d, wgEv, wgD, wgTag);
     // this head's run: its index among the workgroup's runs of the key
     uint32_t o = 0;
     if (head) o = atomicAdd(&wgCnt[e], 1u);
@@ -122,11 +176,7 @@ __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__
     __syncthreads();
     const uint32_t hslot = head ? wgSlot[e] : kNoSlot;
     const uint32_t k = head ? wgBase[e] + o : 0u;            // this run's index in its key
-    const uint64_t H = __ballot(head);
-    const uint64_t le = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);
-    const uint64_t hm = H & le;
-    const int myhead = hm ? 63 - __builtin_clzll(hm) : (int)lane;
-    const uint32_t slot = __shfl(hslot, myhead);
+    const uint32_t slot = __shfl(hslot, run_head_lane(__ballot(head), lane));
     if (h.ok && slot == kNoSlot) {                             // table full / probe timeout
         h.ok = false;
         h.derr = true;
@@ -134,32 +184,9 @@ __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__
     if (live) {
         const u32x4 v = {h.off, h.pl, h.blen, hl};
         st16(reinterpret_cast<uint8_t *>(sc.recs + p), v);
-        if (!h.ok) st16(reinterpret_cast<uint8_t *>(info + p), u32x4{0u, 0u, 0u, hl});   // takes no part
+        if (!h.ok) st_info(info + p, PktInfo{0ull, 0u, hl});   // takes no part
     }
-    // runs of consecutive positions of one key (one slot) within the wave -- they start at
-    // the heads -- filed in the slot's bucket (the run of index 0 lists the slot for the walk)
-    const uint32_t ks = h.ok ? slot : kRoNoSlot;
-    const uint32_t pks = lane_prev(ks, kRoNoSlot), nks = lane_next(ks, kRoNoSlot);
-    const bool rhead = h.ok && (lane == 0 || pks != ks);
-    const bool rtail = h.ok && (lane == 63 || nks != ks);
-    const uint64_t RT = __ballot(rtail);
-    if (rhead) {
-        const uint64_t below = (1ull << lane) - 1ull;
-        const uint32_t len = (uint32_t)__builtin_ctzll(RT & ~below) - lane + 1u;   // to this run's last lane
-        if (k == 0u) sc.active[atomicAdd(&sc.ctr[1], 1u)] = slot;
-        if (k < kRoBucket) {
-            sc.bucket[(size_t)slot * kRoBucket + k] = ((unsigned long long)p << 32) | len;
-        } else {
-            st16(reinterpret_cast<uint8_t *>(sc.runs + p), u32x4{slot, p, len, k});   // at its head's position
-        }
-    }
-    // which lanes of this wave hold an overflow run (every wave writes its word; a flag tells
-    // the place pass to look -- a plain store, not a counter all waves would contend on)
-    const uint64_t OV = __ballot(rhead && k >= kRoBucket);
-    if (lane == 0 && waveLive) {
-        sc.ovMask[wave] = OV;
-        if (OV) sc.ctr[0] = 1u;
-    }
+    ro_file_runs(sc, h.ok, slot, k, p, lane, wave, waveLive);
     wave_stats(R, live && !foreign, (live && !foreign) ? raw.len : 0u, h.bad, h.derr, wave);
 }
 
@@ -177,7 +204,7 @@ constexpr uint32_t kPlaceThreads = 256, kPlaceBlocks = 64, kPlaceLdsSlots = 1638
 __global__ __launch_bounds__(kPlaceThreads) void ro_place_kernel(RoScratch sc, uint32_t T, uint32_t n)
 {
     __shared__ uint32_t base[kPlaceLdsSlots];
-    __shared__ uint32_t part[kPlaceThreads];
+    __shared__ uint32_t part[kPlaceThreads / 64];
     const uint32_t t = threadIdx.x;
     const uint32_t nOver = sc.ctr[0];
     if (blockIdx.x == 0 && t == 0) {
@@ -194,15 +221,8 @@ __global__ __launch_bounds__(kPlaceThreads) void ro_place_kernel(RoScratch sc, u
         const uint32_t c = sc.runCnt[q];
         sum += c > kRoBucket ? c : 0u;
     }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < kPlaceThreads; off <<= 1) {           // inclusive scan
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t b = part[t] - sum;
+    uint32_t all;
+    uint32_t b = block_excl_scan<uint32_t, kPlaceThreads / 64>(sum, part, all);
     for (uint32_t q = s0; q < s1; q++) {
         const uint32_t c = sc.runCnt[q];
         if (inLds) base[q] = b;
@@ -267,9 +287,7 @@ __device__ __forceinline__ void wave_sort_lds(unsigned long long *v, uint32_t la
                     v[ii[t] + j] = x[t];
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
 }
 
@@ -289,9 +307,7 @@ __device__ unsigned long long *ro_sort_runs(const RoScratch &sc, uint32_t slot, 
     while (P < c) P <<= 1;
     if (P <= kRoSortLds) {
         for (uint32_t i = lane; i < P; i += 64u) lds[i] = i < kRoBucket ? bv : (i < c ? ov[i] : ~0ull);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         if (P <= 128u) wave_sort_lds<1>(lds, lane);
         else if (P <= 256u) wave_sort_lds<2>(lds, lane);
         else if (P <= 512u) wave_sort_lds<4>(lds, lane);
@@ -322,19 +338,6 @@ __device__ unsigned long long *ro_sort_runs(const RoScratch &sc, uint32_t slot, 
     return g;
 }
 
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-
 // The positions of a key of more than kRoBucket runs, in arrival order, into the wave's LDS
 // region, without sorting its runs: every run sets its positions' bits in a bitmap over the
 // key's span (LDS atomic ORs), and the set bits read in order are the positions.  Returns
@@ -353,13 +356,11 @@ __device__ uint32_t ro_positions(const RoScratch &sc, uint32_t slot, uint32_t c,
     }
     mn = wave_min_u32(mn);
     mx = wave_max_u32(mx);
-    tl = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(tl), 63);
+    tl = readlane(wave_incl_scan(tl), 63);
     const uint32_t words = (mx - mn + 63u) / 64u;
     if ((size_t)words * 8u + (size_t)tl * 4u > (size_t)ldsWords * 8u) return 0u;     // wave-uniform
     for (uint32_t i = lane; i < words; i += 64u) lds[i] = 0ull;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     for (uint32_t i = lane; i < c; i += 64u) {
         const unsigned long long r = i < kRoBucket ? bv : ov[i];
         const uint32_t b = (uint32_t)(r >> 32) - mn, ln = (uint32_t)r;   // 1..64 positions
@@ -368,9 +369,7 @@ __device__ uint32_t ro_positions(const RoScratch &sc, uint32_t slot, uint32_t c,
         atomicOr(&lds[b >> 6], m << o);
         if (o + ln > 64u) atomicOr(&lds[(b >> 6) + 1u], m >> (64u - o));
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // each lane reads a contiguous block of words; a wave scan of their counts places them
     const uint32_t wpl = (words + 63u) / 64u, w0 = lane * wpl, w1 = min(w0 + wpl, words);
     uint32_t cnt = 0;
@@ -379,9 +378,7 @@ __device__ uint32_t ro_positions(const RoScratch &sc, uint32_t slot, uint32_t c,
     uint32_t *pos = reinterpret_cast<uint32_t *>(lds + words);
     for (uint32_t x = w0; x < w1; x++)
         for (unsigned long long m = lds[x]; m; m &= m - 1ull) pos[at++] = mn + x * 64u + (uint32_t)__builtin_ctzll(m);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // the list starts at lds + words: move it to the front (the walk reads it from there)
     uint32_t *dst = reinterpret_cast<uint32_t *>(lds);
     for (uint32_t i = lane; i < tl; i += 64u) {
@@ -390,10 +387,192 @@ __device__ uint32_t ro_positions(const RoScratch &sc, uint32_t slot, uint32_t c,
         __builtin_amdgcn_wave_barrier();
         dst[i] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     return tl;
+}
+
+// The item in progress under a key (the device form of the reference's EventQueueItem) and
+// the walk's tallies; wave-uniform.
+struct RoItem {
+    bool item;                    // an item is in progress
+    uint64_t boff, cur, created;  // its buffer (arena offset, or kNoBuf), curBytes, firstSegment
+    uint32_t ibytes, frags;       // its length (the bufferLength of the fragment that started it), fragments
+    long long live;               // net change of items in progress
+    uint32_t derr;                // fragments that overran their item
+};
+__device__ __forceinline__ RoItem ro_item_load(const ReasSlot *sl)
+{
+    RoItem it;
+    it.item = sl->bvalid == 1u;                                // an item in progress from an earlier batch
+    it.boff = sl->bufOff;
+    it.ibytes = sl->bytes;
+    it.cur = it.item ? (sl->acc & kAccBytesMask) : 0ull;
+    it.frags = it.item ? (uint32_t)(sl->acc >> kAccFragShift) : 0u;
+    it.created = sl->created;
+    it.live = 0;
+    it.derr = 0;
+    return it;
+}
+__device__ __forceinline__ void ro_item_store(ReasSlot *sl, const RoItem &it)
+{
+    if (it.item) {
+        sl->bufOff = it.boff;
+        sl->bytes = it.ibytes;
+        sl->bvalid = 1u;
+        sl->acc = ((unsigned long long)it.frags << kAccFragShift) | (it.cur & kAccBytesMask);
+        sl->created = it.created;
+    } else {
+        sl->state = kDone;                                     // no item left under this key
+    }
+}
+
+// The key a wave walks, and where its work records go.
+struct RoKey {
+    uint64_t ev, now;
+    uint32_t slot, d;
+    PktInfo *info;
+    FinishRec *fin;
+};
+
+// The buffer of a new item of blen bytes: lane 0 claims it from the arena, every lane gets
+// it (kNoBuf, with the error flag set, when the arena is full).
+__device__ __forceinline__ uint64_t ro_new_buffer(const ReasDev &R, uint32_t blen, uint32_t lane)
+{
+    const uint64_t need = ((uint64_t)blen + 255ull) & ~255ull;
+    uint64_t nb = 0;
+    if (lane == 0) nb = atomicAdd(&R.ctl->arenaTop, (unsigned long long)(need ? need : 256ull));
+    nb = readlane_u64(nb, 0);
+    if (nb + blen > R.arenaBytes) {
+        if (lane == 0) atomicOr(&R.ctl->errorFlags, 2u);
+        nb = kNoBuf;
+    }
+    return nb;
+}
+
+// One chunk of 64 datagrams of the key, in arrival order: datagrams [base, base + 64) of the
+// tot being walked, lane by lane (q: position, rc: record).
+__device__ __forceinline__ void ro_walk_chunk(const ReasDev &R, const RoKey &key, RoItem &it, uint32_t tot, uint32_t base,
+                                              uint32_t q, const RoRec &rc, uint32_t lane)
+{
+    const bool valid = base + lane < tot;
+    const uint32_t nv = (tot - base < 64u) ? tot - base : 64u;
+    for (uint32_t t = 0; t < nv;) {
+        if (!it.item || readlane(rc.off, t) == 0u) {
+            // a new item (EventQueueItem(rehdr), hpp:89-98); at offset 0 it replaces the
+            // one in progress (cpp:361-369), dropped without a lost record
+            if (it.item) it.live--;
+            const uint32_t blen = readlane(rc.blen, t);
+            it.boff = ro_new_buffer(R, blen, lane);
+            it.ibytes = blen;
+            it.cur = 0;
+            it.frags = 0;
+            it.created = key.now;
+            it.item = true;
+            it.live++;
+        }
+        const uint64_t zm = __ballot(valid && rc.off == 0u && lane > t);
+        const uint32_t v = zm ? (uint32_t)__builtin_ctzll(zm) : nv;      // next item start
+        const bool inseg = lane >= t && lane < v;
+        const bool viol = inseg && (uint64_t)rc.off + rc.plen > it.ibytes;
+        const uint32_t P = wave_incl_scan((inseg && !viol) ? rc.plen : 0u);
+        const uint64_t cm = __ballot(inseg && !viol && it.cur + P == (uint64_t)it.ibytes);
+        const uint32_t end = cm ? (uint32_t)__builtin_ctzll(cm) + 1u : v;
+        const bool inr = lane >= t && lane < end;
+        it.frags += (uint32_t)__builtin_popcountll(__ballot(inr && !viol));     // cpp:398-400
+        it.derr += (uint32_t)__builtin_popcountll(__ballot(inr && viol));
+        it.cur += readlane(P, end - 1u);
+        const bool comp = cm && lane == end - 1u;
+        if (inr) {
+            PktInfo pi{0ull, 0u, rc.hl};
+            if (!viol && it.boff != kNoBuf) {
+                pi.dst = (uint64_t)(R.arena + it.boff + rc.off);
+                pi.plen = rc.plen;
+            }
+            if (comp) {                                        // cpp:403: complete, erase, enqueue
+                FinishRec f;
+                f.ev = key.ev;
+                f.boff = it.boff;
+                f.slot = key.slot | kFinKeepSlot;
+                f.bytes = it.ibytes;
+                f.frags = it.frags;
+                f.d = key.d;
+                key.fin[q] = f;
+            }
+            st_info(key.info + q, pi, comp ? kPktCompletes : 0u);
+        }
+        if (cm) it.item = false;                               // inProgress-- in complete_event
+        t = end;
+    }
+}
+
+// The walk of tot datagrams of the key, 64 at a time; q_of(base) is the position of datagram
+// base + lane.  The records of the next kRoAhead - 1 chunks are in flight while a chunk is
+// walked (the walk is a chain of dependent chunks over few waves: latency, not bandwidth,
+// bounds it).  The ring is indexed statically (unrolled by kRoAhead); a chunk's slot is
+// reloaded after the chunk is walked.  (Round 5: staging a key's records in LDS by LDS-DMA,
+// 16 chunks per wait, measured 16.6 against this ring's 15.5 us per launch: the chunks' own
+// work, ~0.8 us each at one wave per CU, not their loads, bounds the walk)
+template <typename PosOf>
+__device__ __forceinline__ void ro_walk_ring(const ReasDev &R, const RoKey &key, RoItem &it,
+                                             const RoRec *__restrict__ recs, uint32_t tot, uint32_t lane, PosOf q_of)
+{
+    uint32_t qr[kRoAhead];
+    RoRec rr[kRoAhead];
+#pragma unroll
+    for (uint32_t i = 0; i < kRoAhead; i++) {
+        qr[i] = q_of(i * 64u);
+        rr[i] = RoRec{0u, 0u, 0u, 0u};
+        if (i * 64u + lane < tot) rr[i] = recs[qr[i]];
+    }
+    for (uint32_t b0 = 0; b0 < tot; b0 += kRoAhead * 64u) {
+#pragma unroll
+        for (uint32_t i = 0; i < kRoAhead; i++) {
+            const uint32_t base = b0 + i * 64u;
+            if (base < tot) {                                  // wave-uniform
+                ro_walk_chunk(R, key, it, tot, base, qr[i], rr[i], lane);
+                const uint32_t nxt = base + kRoAhead * 64u;
+                if (nxt < tot) {
+                    qr[i] = q_of(nxt);
+                    if (nxt + lane < tot) rr[i] = recs[qr[i]];
+                }
+            }
+        }
+    }
+}
+
+// Position source of the ring over m <= 64 runs in position order, one per lane (rex: the
+// exclusive prefix of their lengths, rstart: their starts).  Datagram base + lane lies in the
+// last run whose prefix is <= it.  The runs that meet the chunk [base, base + 64) are ra..rb
+// (usually two): a uniform loop over them with scalar reads, no per-lane search
+struct RoRunPos {
+    uint32_t m, rex, rstart, lane;
+    __device__ __forceinline__ uint32_t operator()(uint32_t base) const
+    {
+        const uint32_t g = base + lane;
+        const uint64_t b0 = __ballot(lane < m && rex <= base), b1 = __ballot(lane < m && rex < base + 64u);
+        const int ra = b0 ? 63 - __builtin_clzll(b0) : 0, rb = b1 ? 63 - __builtin_clzll(b1) : 0;
+        uint32_t qb = 0;
+        for (int r = ra; r <= rb; r++) {
+            const uint32_t sr = readlane(rex, (uint32_t)r);
+            const uint32_t st = readlane(rstart, (uint32_t)r);
+            if (g >= sr) qb = st - sr;
+        }
+        return qb + g;
+    }
+};
+
+// Order the m runs of a bucket (start << 32 | length, one per lane) by start (the starts are
+// distinct): each run's rank is the number of runs that start before it (m scalar reads),
+// then one push per word to lane rank
+__device__ __forceinline__ unsigned long long ro_order_bucket(unsigned long long rv, uint32_t m, uint32_t lane)
+{
+    const uint32_t mys = (uint32_t)(rv >> 32);
+    uint32_t rank = 0;
+    for (uint32_t r = 0; r < m; r++) rank += readlane(mys, r) < mys ? 1u : 0u;
+    if (lane >= m) rank = lane;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute((int)(rank * 4u), (int)(uint32_t)rv);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_permute((int)(rank * 4u), (int)mys);
+    return ((unsigned long long)hi << 32) | lo;
 }
 
 // WB waves per workgroup, LW 8-byte words of LDS per wave (the position bitmap and list, or
@@ -424,165 +603,29 @@ __global__ __launch_bounds__(WB * 64) void ro_walk_kernel(ReasDev R, RoScratch s
     }
     const RoRec *__restrict__ recs = sc.recs;
     ReasSlot *sl = R.slots + slot;
-    const uint64_t ev = sl->eventNum;
-    const uint32_t d = sl->dataId;
-    bool item = sl->bvalid == 1u;                              // an item in progress from an earlier batch
-    uint64_t boff = sl->bufOff;
-    uint32_t ibytes = sl->bytes;
-    uint64_t cur = item ? (sl->acc & kAccBytesMask) : 0ull;
-    uint32_t frags = item ? (uint32_t)(sl->acc >> kAccFragShift) : 0u;
-    uint64_t created = sl->created;
-    long long live = 0;                                        // net change of items in progress
-    uint32_t derr = 0;
-    uint32_t tot = 0;                                          // datagrams of the current walk
-    // one chunk of 64 datagrams of the key, in arrival order (q: position, rc: record)
-    auto walk_chunk = [&](uint32_t base, uint32_t q, const RoRec &rc) {
-        const bool valid = base + lane < tot;
-        const uint32_t nv = (tot - base < 64u) ? tot - base : 64u;
-        for (uint32_t t = 0; t < nv;) {
-            if (!item || (uint32_t)__builtin_amdgcn_readlane((int)rc.off, (int)t) == 0u) {
-                // a new item (EventQueueItem(rehdr), hpp:89-98); at offset 0 it replaces the
-                // one in progress (cpp:361-369), dropped without a lost record
-                if (item) live--;
-                const uint32_t blen = (uint32_t)__builtin_amdgcn_readlane((int)rc.blen, (int)t);
-                const uint64_t need = ((uint64_t)blen + 255ull) & ~255ull;
-                uint64_t nb = 0;
-                if (lane == 0) nb = atomicAdd(&R.ctl->arenaTop, (unsigned long long)(need ? need : 256ull));
-                nb = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(nb >> 32), 0) << 32) |
-                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)nb, 0);
-                if (nb + blen > R.arenaBytes) {
-                    if (lane == 0) atomicOr(&R.ctl->errorFlags, 2u);
-                    nb = kNoBuf;
-                }
-                boff = nb;
-                ibytes = blen;
-                cur = 0;
-                frags = 0;
-                created = now;
-                item = true;
-                live++;
-            }
-            const uint64_t zm = __ballot(valid && rc.off == 0u && lane > t);
-            const uint32_t v = zm ? (uint32_t)__builtin_ctzll(zm) : nv;      // next item start
-            const bool inseg = lane >= t && lane < v;
-            const bool viol = inseg && (uint64_t)rc.off + rc.plen > ibytes;
-            const uint32_t P = wave_incl_scan((inseg && !viol) ? rc.plen : 0u);
-            const uint64_t cm = __ballot(inseg && !viol && cur + P == (uint64_t)ibytes);
-            const uint32_t end = cm ? (uint32_t)__builtin_ctzll(cm) + 1u : v;
-            const bool inr = lane >= t && lane < end;
-            frags += (uint32_t)__builtin_popcountll(__ballot(inr && !viol));     // cpp:398-400
-            derr += (uint32_t)__builtin_popcountll(__ballot(inr && viol));
-            cur += (uint32_t)__builtin_amdgcn_readlane((int)P, (int)(end - 1u));
-            const bool comp = cm && lane == end - 1u;
-            if (inr) {
-                PktInfo pi{0ull, 0u, rc.hl};
-                if (!viol && boff != kNoBuf) {
-                    pi.dst = (uint64_t)(R.arena + boff + rc.off);
-                    pi.plen = rc.plen;
-                }
-                if (comp) {                                    // cpp:403: complete, erase, enqueue
-                    FinishRec f;
-                    f.ev = ev;
-                    f.boff = boff;
-                    f.slot = slot | kFinKeepSlot;
-                    f.bytes = ibytes;
-                    f.frags = frags;
-                    f.d = d;
-                    fin[q] = f;
-                    pi.hl |= kPktCompletes;
-                }
-                st16(reinterpret_cast<uint8_t *>(info + q), u32x4{(uint32_t)pi.dst, (uint32_t)(pi.dst >> 32), pi.plen, pi.hl});
-            }
-            if (cm) item = false;                              // inProgress-- in complete_event
-            t = end;
-        }
-    };
-    // the records of the next kRoAhead - 1 chunks are in flight while a chunk is walked (the
-    // walk is a chain of dependent chunks over few waves: latency, not bandwidth, bounds it).
-    // The ring is indexed statically (unrolled by kRoAhead); a chunk's slot is reloaded after
-    // the chunk is walked.  (Round 5: staging a key's records in LDS by LDS-DMA, 16 chunks per
-    // wait, measured 16.6 against this ring's 15.5 us per launch: the chunks' own work, ~0.8
-    // us each at one wave per CU, not their loads, bounds the walk)
-    auto walk_ring = [&](auto q_of) {
-    uint32_t qr[kRoAhead];
-    RoRec rr[kRoAhead];
-#pragma unroll
-    for (uint32_t i = 0; i < kRoAhead; i++) {
-        qr[i] = q_of(i * 64u);
-        rr[i] = RoRec{0u, 0u, 0u, 0u};
-        if (i * 64u + lane < tot) rr[i] = recs[qr[i]];
-    }
-    for (uint32_t b0 = 0; b0 < tot; b0 += kRoAhead * 64u) {
-#pragma unroll
-        for (uint32_t i = 0; i < kRoAhead; i++) {
-            const uint32_t base = b0 + i * 64u;
-            if (base < tot) {                                  // wave-uniform
-                walk_chunk(base, qr[i], rr[i]);
-                const uint32_t nxt = base + kRoAhead * 64u;
-                if (nxt < tot) {
-                    qr[i] = q_of(nxt);
-                    if (nxt + lane < tot) rr[i] = recs[qr[i]];
-                }
-            }
-        }
-    }
-    };
+    const RoKey key{sl->eventNum, now, slot, sl->dataId, info, fin};
+    RoItem it = ro_item_load(sl);
     if (nPos) {
         // the key's positions in arrival order, from its position bitmap
         const uint32_t *pos = reinterpret_cast<const uint32_t *>(lds);
-        tot = nPos;
-        walk_ring([&](uint32_t base) -> uint32_t { return base + lane < tot ? pos[base + lane] : 0u; });
+        ro_walk_ring(R, key, it, recs, nPos, lane, [=](uint32_t base) { return base + lane < nPos ? pos[base + lane] : 0u; });
     } else {
-    for (uint32_t r0 = 0; r0 < nRuns; r0 += 64u) {
-    // this batch of the key's runs, in position order: start << 32 | length per lane
-    const uint32_t m = (nRuns - r0 < 64u) ? nRuns - r0 : 64u;
-    unsigned long long rv = (lane < m) ? (inBucket ? bv : runsOf[r0 + lane]) : ~0ull;
-    if (inBucket) {
-        // order the bucket by start (the starts are distinct): each run's rank is the number
-        // of runs that start before it (m scalar reads), then one push per word to lane rank
-        const uint32_t mys = (uint32_t)(rv >> 32);
-        uint32_t rank = 0;
-        for (uint32_t r = 0; r < m; r++) rank += (uint32_t)__builtin_amdgcn_readlane((int)mys, (int)r) < mys ? 1u : 0u;
-        if (lane >= m) rank = lane;
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_permute((int)(rank * 4u), (int)(uint32_t)rv);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_permute((int)(rank * 4u), (int)mys);
-        rv = ((unsigned long long)hi << 32) | lo;
-    }
-    const uint32_t rlen = (uint32_t)rv & 0xFFFFFFFFu, rstart = (uint32_t)(rv >> 32);
-    const uint32_t rl = lane < m ? rlen : 0u;
-    const uint32_t rin = wave_incl_scan(rl), rex = rin - rl;
-    tot = (uint32_t)__builtin_amdgcn_readlane((int)rin, 63);
-    // position of datagram base + lane of this batch of runs: in the last run whose prefix
-    // is <= it.  The runs that meet the chunk [base, base + 64) are r0..r1 (usually two): a
-    // uniform loop over them with scalar reads, no per-lane search
-    auto pos_of = [&](uint32_t base) -> uint32_t {
-        const uint32_t g = base + lane;
-        const uint64_t b0 = __ballot(lane < m && rex <= base), b1 = __ballot(lane < m && rex < base + 64u);
-        const int r0 = b0 ? 63 - __builtin_clzll(b0) : 0, r1 = b1 ? 63 - __builtin_clzll(b1) : 0;
-        uint32_t qb = 0;
-        for (int r = r0; r <= r1; r++) {
-            const uint32_t sr = (uint32_t)__builtin_amdgcn_readlane((int)rex, r);
-            const uint32_t st = (uint32_t)__builtin_amdgcn_readlane((int)rstart, r);
-            if (g >= sr) qb = st - sr;
+        for (uint32_t r0 = 0; r0 < nRuns; r0 += 64u) {
+            // this batch of the key's runs, in position order: start << 32 | length per lane
+            const uint32_t m = (nRuns - r0 < 64u) ? nRuns - r0 : 64u;
+            unsigned long long rv = (lane < m) ? (inBucket ? bv : runsOf[r0 + lane]) : ~0ull;
+            if (inBucket) rv = ro_order_bucket(rv, m, lane);
+            const uint32_t rlen = (uint32_t)rv & 0xFFFFFFFFu, rstart = (uint32_t)(rv >> 32);
+            const uint32_t rl = lane < m ? rlen : 0u;
+            const uint32_t rin = wave_incl_scan(rl), rex = rin - rl;
+            ro_walk_ring(R, key, it, recs, readlane(rin, 63), lane, RoRunPos{m, rex, rstart, lane});
         }
-        return qb + g;
-    };
-    walk_ring(pos_of);
-    }
     }
     if (lane == 0) {
         sc.runCnt[slot] = 0u;                                  // next batch
-        if (item) {
-            sl->bufOff = boff;
-            sl->bytes = ibytes;
-            sl->bvalid = 1u;
-            sl->acc = ((unsigned long long)frags << kAccFragShift) | (cur & kAccBytesMask);
-            sl->created = created;
-        } else {
-            sl->state = kDone;                                 // no item left under this key
-        }
-        if (live) atomicAdd(occ_in_progress(R, slot), (unsigned long long)live);
-        if (derr) atomicAdd(&R.shards[slot % kShards].dataErrCnt, (unsigned long long)derr);
+        ro_item_store(sl, it);
+        if (it.live) atomicAdd(occ_in_progress(R, slot), (unsigned long long)it.live);
+        if (it.derr) atomicAdd(&R.shards[slot % kShards].dataErrCnt, (unsigned long long)it.derr);
     }
 }
 

@@ -34,11 +34,7 @@ __device__ __forceinline__ void classify_wave_to_work(const ReasDev &R, const ui
     const RawHdr raw = load_hdr(R, pkts, stride, lens, p0 + ((lane < gn) ? lane : 0u));
     const Classified cl = classify_wave(R, raw, stride, lane < gn, now, wave);
     const bool done = completes(cl);
-    if (lane < gn) {
-        const u32x4 v = {(uint32_t)cl.info.dst, (uint32_t)(cl.info.dst >> 32), cl.info.plen,
-                         cl.info.hl | (done ? kPktCompletes : 0u)};
-        st16(reinterpret_cast<uint8_t *>(info + p0 + lane), v);
-    }
+    if (lane < gn) st_info(info + p0 + lane, cl.info, done ? kPktCompletes : 0u);
     if (done) {
         FinishRec f;
         f.ev = cl.ev;

@@ -77,6 +77,11 @@ __device__ __forceinline__ PktInfo ld_info(const PktInfo *p)
     r.hl = v.w;
     return r;
 }
+// ... and its packing, in one 16-byte store; hlFlags: flag bits or-ed into hl (kPktCompletes)
+__device__ __forceinline__ void st_info(PktInfo *p, const PktInfo &pi, uint32_t hlFlags = 0)
+{
+    st16(reinterpret_cast<uint8_t *>(p), u32x4{(uint32_t)pi.dst, (uint32_t)(pi.dst >> 32), pi.plen, pi.hl | hlFlags});
+}
 
 // Destination-aligned form of the same copy: chunk c of a payload whose phase in its event
 // buffer is a (= bufferOffset mod 16; event buffers are 256-byte aligned in a 256-byte

@@ -175,7 +175,6 @@ __global__ __launch_bounds__(kBlock) void relay_plan_kernel(ReasDev R, uint32_t 
 {
     __shared__ uint32_t waveSum[kBlock / 64];
     __shared__ uint32_t sN;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) {
         uint32_t stored = ld_agent(&R.ctl->nCompleted);
         if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
@@ -190,29 +189,21 @@ __global__ __launch_bounds__(kBlock) void relay_plan_kernel(ReasDev R, uint32_t 
         e2sar_hip_event_rec rec{};
         if (i < n) rec = R.completed[first + i];
         const uint32_t np = (i < n) ? rec.bytes / maxPld + (rec.bytes % maxPld != 0u) : 0u;
-        uint32_t inc = np;                                   // inclusive scan in the wave
-#pragma unroll
-        for (uint32_t o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        if (lane == 63) waveSum[wv] = inc;
-        __syncthreads();
-        uint32_t before = carry;
-        for (uint32_t w = 0; w < wv; w++) before += waveSum[w];
+        uint32_t step;
+        const uint32_t before = block_excl_scan<uint32_t, kBlock / 64>(np, waveSum, step);
         if (i < n) {
             e2sar_hip_seg_event d;
             d.data = R.arena + rec.arenaOffset;
             d.eventNum = rec.eventNum;
             d.lbTick = lbTick;
             d.bytes = rec.bytes;
-            d.pktBase = before + inc - np;
+            d.pktBase = carry + before;
             d.dataId = rec.dataId;
             d.entropy = (uint16_t)(entropyBase + i);
             d.reserved = 0;
             out[i] = d;
         }
-        for (uint32_t w = 0; w < kBlock / 64; w++) carry += waveSum[w];
+        carry += step;
         __syncthreads();
     }
     if (threadIdx.x == 0) {

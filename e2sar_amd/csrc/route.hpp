@@ -63,39 +63,23 @@ __global__ __launch_bounds__(kBlock) void route_hist_kernel(const uint8_t *__res
 }
 
 // one block: exclusive scans -> per-block bases, per-destination counts and bases.
-// For each destination the nBlocks counts are scanned 256 at a time (wave prefix sums
-// through LDS, a running carry between tiles), so the scan costs nBlocks/256 block steps
-// per destination instead of nBlocks dependent loads.
-// Append mode (cap > 0): rank d's span is a region of cap slots at d * cap that successive
-// batches append to; destBase[d] = d * cap + running[d], then running[d] += this batch's
-// count (the count keeps growing past cap, so the caller sees an overflow; the pack kernel
-// writes nothing past a region's end).  counts may be NULL in append mode.
+// For each destination the nBlocks counts are scanned 256 at a time (block_excl_scan, a
+// running carry between tiles), so the scan costs nBlocks/256 block steps per destination
+// instead of nBlocks dependent loads.
 __global__ __launch_bounds__(kBlock) void route_scan_kernel(uint32_t *__restrict__ blockHist, uint32_t nBlocks,
                                                             uint32_t world, uint32_t *__restrict__ counts,
-                                                            uint32_t *__restrict__ destBase, uint32_t cap,
-                                                            uint32_t *__restrict__ running)
+                                                            uint32_t *__restrict__ destBase)
 {
     __shared__ uint32_t waveSum[kBlock / 64];
     __shared__ uint32_t tot[kMaxWorld];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     for (uint32_t d = 0; d < world; d++) {
         uint32_t carry = 0;
         for (uint32_t b0 = 0; b0 < nBlocks; b0 += kBlock) {
             const uint32_t b = b0 + threadIdx.x;
             const uint32_t c = (b < nBlocks) ? blockHist[(uint64_t)b * world + d] : 0u;
-            uint32_t inc = c;                                 // inclusive scan in the wave
-#pragma unroll
-            for (uint32_t o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(inc, o);
-                if (lane >= o) inc += y;
-            }
-            if (lane == 63) waveSum[wv] = inc;
-            __syncthreads();
-            uint32_t before = carry;
-            for (uint32_t w = 0; w < wv; w++) before += waveSum[w];
-            if (b < nBlocks) blockHist[(uint64_t)b * world + d] = before + inc - c;
-            uint32_t tile = 0;
-            for (uint32_t w = 0; w < kBlock / 64; w++) tile += waveSum[w];
+            uint32_t tile;
+            const uint32_t before = block_excl_scan<uint32_t, kBlock / 64>(c, waveSum, tile);
+            if (b < nBlocks) blockHist[(uint64_t)b * world + d] = carry + before;
             carry += tile;
             __syncthreads();
         }
@@ -108,14 +92,8 @@ __global__ __launch_bounds__(kBlock) void route_scan_kernel(uint32_t *__restrict
     if (threadIdx.x == 0) {
         uint32_t run = 0;
         for (uint32_t d = 0; d < world; d++) {
-            if (cap) {
-                const uint32_t have = running[d];
-                destBase[d] = d * cap + have;
-                running[d] = have + tot[d];
-            } else {
-                destBase[d] = run;
-                run += tot[d];
-            }
+            destBase[d] = run;
+            run += tot[d];
         }
     }
 }
@@ -131,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void route_pack_kernel(const uint8_t *__res
                                                             const uint32_t *__restrict__ lens, uint32_t n, int withLB,
                                                             uint32_t world, uint32_t self, int excludeSelf,
                                                             const uint32_t *__restrict__ blockBase,
-                                                            const uint32_t *__restrict__ destBase, uint32_t cap,
+                                                            const uint32_t *__restrict__ destBase,
                                                             uint8_t *__restrict__ out, uint32_t *__restrict__ outLens)
 {
     __shared__ uint32_t pos[kBlock];
@@ -152,10 +130,8 @@ __global__ __launch_bounds__(kBlock) void route_pack_kernel(const uint8_t *__res
         uint32_t before = 0;
         for (uint32_t w = 0; w < wv; w++) before += waveCnt[w][dest];
         const uint32_t q = destBase[dest] + blockBase[(uint64_t)g * world + dest] + before + rank;
-        if (!cap || q < (dest + 1u) * cap) {                  // append mode: nothing past the region
-            pos[threadIdx.x] = q;
-            if (sl == 0) outLens[q] = lens[p];
-        }
+        pos[threadIdx.x] = q;
+        if (sl == 0) outLens[q] = lens[p];
     }
     // foreign-only routing leaves most blocks with nothing to move at small world sizes
     if (!__syncthreads_or(dest != kNoDest)) return;

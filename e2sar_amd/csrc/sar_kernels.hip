@@ -423,9 +423,9 @@ hipError_t launch_reas_classify(const ReasDev &R, const uint8_t *pkts, uint32_t 
                                 uint32_t n, uint64_t now, void *work, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    uint8_t *w = static_cast<uint8_t *>(work);
+    const WorkView w = work_view(work, n);
     hipLaunchKernelGGL(reas_classify_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, R, pkts, stride, lens,
-                       n, now, reinterpret_cast<PktInfo *>(w), reinterpret_cast<FinishRec *>(w + work_fin_off(n)));
+                       n, now, w.info, w.fin);
     return hipGetLastError();
 }
 
@@ -474,16 +474,14 @@ hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t s
                                const void *work, hipStream_t stream, bool nt)
 {
     if (n == 0) return hipSuccess;
-    const uint8_t *w = static_cast<const uint8_t *>(work);
+    const WorkView w = work_view(work, n);
     uint32_t blocks = 0;
     const uint32_t G = scatter_geometry(stride, n, blocks);
-    const PktInfo *info = reinterpret_cast<const PktInfo *>(w);
-    const FinishRec *fin = reinterpret_cast<const FinishRec *>(w + work_fin_off(n));
     with_scatter_variant(stride, nt, [&](auto v) {
         using V = decltype(v);
         const auto kernel = reas_scatter_kernel<V::U, V::NT, V::STAGE, V::TB>;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
-                           n, G, info, fin);
+                           n, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
     });
     return hipGetLastError();
 }
@@ -494,8 +492,7 @@ hipError_t launch_reas_scatter_classify(const ReasDev &R, uint32_t stride, const
 {
     if (cn == 0) return launch_reas_scatter(R, spk, stride, sn, swork, stream, nt);
     if (sn == 0) return launch_reas_classify(R, cpk, stride, clens, cn, now, cwork, stream);
-    const uint8_t *sw = static_cast<const uint8_t *>(swork);
-    uint8_t *cw = static_cast<uint8_t *>(cwork);
+    const WorkView sw = work_view(swork, sn), cw = work_view(cwork, cn);
     uint32_t sblocks = 0;
     const uint32_t G = scatter_geometry(stride, sn, sblocks);
     const uint32_t nCls = (cdiv(cn, (uint32_t)scatter_tb(stride)) + 7u) & ~7u;     // multiples of 8: see xcd_runs
@@ -510,11 +507,8 @@ hipError_t launch_reas_scatter_classify(const ReasDev &R, uint32_t stride, const
         using V = decltype(v);
         const auto kernel = reas_scatter_classify_kernel<V::U, V::NT, V::STAGE, V::TB>;
         hipLaunchKernelGGL(kernel, dim3(nCls + sblocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, stride,
-                           spk, sn, G,
-                           reinterpret_cast<const PktInfo *>(sw),
-                           reinterpret_cast<const FinishRec *>(sw + work_fin_off(sn)), cpk, clens, cn, now,
-                           reinterpret_cast<PktInfo *>(cw), reinterpret_cast<FinishRec *>(cw + work_fin_off(cn)), nCls,
-                           clsStart);
+                           spk, sn, G, (const PktInfo *)sw.info, (const FinishRec *)sw.fin, cpk, clens, cn, now, cw.info,
+                           cw.fin, nCls, clsStart);
     });
     return hipGetLastError();
 }
@@ -524,17 +518,17 @@ hipError_t launch_ro_classify(const ReasDev &R, const uint8_t *pkts, uint32_t st
                               hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    if (ro_scratch_bytes(n, R.tableSlots) > scratchBytes) return hipErrorInvalidValue;
-    uint8_t *w = static_cast<uint8_t *>(work);
-    PktInfo *info = reinterpret_cast<PktInfo *>(w);
-    const RoScratch sc = ro_scratch_layout(scratch, n, R.tableSlots);
+    size_t need;
+    const RoScratch sc = ro_scratch_layout(scratch, n, R.tableSlots, &need);
+    if (need > scratchBytes) return hipErrorInvalidValue;
+    const WorkView w = work_view(work, n);
     hipLaunchKernelGGL((ro_key_kernel<kRoKeyBlock>), dim3(cdiv(n, (uint32_t)kRoKeyBlock)), dim3(kRoKeyBlock), 0, stream,
-                       R, pkts, stride, lens, n, now, sc, info);
+                       R, pkts, stride, lens, n, now, sc, w.info);
     hipLaunchKernelGGL(ro_place_kernel, dim3(kPlaceBlocks), dim3(kPlaceThreads), 0, stream, sc, R.tableSlots, n);
     // one wave per key: at most min(n, tableSlots) keys
     const uint32_t waves = n < R.tableSlots ? n : R.tableSlots;
-    hipLaunchKernelGGL((ro_walk_kernel<1, kRoWalkLds>), dim3(waves), dim3(64), 0, stream, R, sc, R.tableSlots, now, info,
-                       reinterpret_cast<FinishRec *>(w + work_fin_off(n)));
+    hipLaunchKernelGGL((ro_walk_kernel<1, kRoWalkLds>), dim3(waves), dim3(64), 0, stream, R, sc, R.tableSlots, now, w.info,
+                       w.fin);
     return hipGetLastError();
 }
 
@@ -581,20 +575,18 @@ size_t route_workspace_bytes(uint32_t n, uint32_t world)
 
 hipError_t launch_route(const uint8_t *pkts, uint32_t stride, const uint32_t *lens, uint32_t n, int withLB,
                         uint32_t world, uint32_t self, int excludeSelf, uint8_t *out, uint32_t *outLens,
-                        uint32_t *counts, void *workspace, hipStream_t stream, uint32_t cap, uint32_t *running)
+                        uint32_t *counts, void *workspace, hipStream_t stream)
 {
     if (world == 0 || world > kMaxWorld || self >= world) return hipErrorInvalidValue;
-    if (cap && (uint64_t)cap * world > 0xFFFFFFFFull) return hipErrorInvalidValue;
     if (n == 0) return counts ? launch_zero_words(counts, world, stream) : hipSuccess;
     const uint32_t nb = cdiv(n, kBlock);
     uint32_t *blockHist = static_cast<uint32_t *>(workspace);
     uint32_t *destBase = blockHist + (size_t)nb * world;
     hipLaunchKernelGGL(route_hist_kernel, dim3(nb), dim3(kBlock), 0, stream, pkts, stride, lens, n, withLB, world,
                        self, excludeSelf, blockHist);
-    hipLaunchKernelGGL(route_scan_kernel, dim3(1), dim3(kBlock), 0, stream, blockHist, nb, world, counts, destBase,
-                       cap, running);
+    hipLaunchKernelGGL(route_scan_kernel, dim3(1), dim3(kBlock), 0, stream, blockHist, nb, world, counts, destBase);
     hipLaunchKernelGGL(route_pack_kernel, dim3(nb * kPackSplit), dim3(kBlock), 0, stream, pkts, stride, lens, n, withLB, world,
-                       self, excludeSelf, blockHist, destBase, cap, out, outLens);
+                       self, excludeSelf, blockHist, destBase, out, outLens);
     return hipGetLastError();
 }
 

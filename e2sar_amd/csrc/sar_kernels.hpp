@@ -129,6 +129,15 @@ static_assert(sizeof(FinishRec) == 32, "two dwordx4 per record");
 //   [work_fin_off(n), + 32n)  FinishRec per datagram (written only by completing run tails)
 inline size_t work_fin_off(uint32_t n) { return ((size_t)n * sizeof(PktInfo) + 255) & ~(size_t)255; }
 inline size_t work_bytes(uint32_t n) { return work_fin_off(n) + (size_t)n * sizeof(FinishRec); }
+struct WorkView {
+    PktInfo *info;
+    FinishRec *fin;
+};
+inline WorkView work_view(const void *work, uint32_t n)   // (a launch that only reads takes them as const)
+{
+    uint8_t *w = static_cast<uint8_t *>(const_cast<void *>(work));
+    return {reinterpret_cast<PktInfo *>(w), reinterpret_cast<FinishRec *>(w + work_fin_off(n))};
+}
 
 // Reference-order mode: per-datagram record of ro_key_kernel, and the scratch it needs for a
 // batch of n datagrams and a table of T slots.  Round 5: no sort of the datagrams -- the key
@@ -160,33 +169,36 @@ struct RoScratch {
 inline size_t ro_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // the scratch's first bytes that must be zero before its first batch (later batches leave them zero)
 inline size_t ro_zero_bytes(uint32_t T) { return 256 + ro_align(4ull * T); }
+// The layout, stated once: the regions in order, each padded to 256 bytes; *bytes is where
+// the last one ends.  base may be null when only the size is wanted (ro_scratch_bytes).
+inline RoScratch ro_scratch_layout(void *base, uint32_t n, uint32_t T, size_t *bytes = nullptr)
+{
+    uint8_t *const b = static_cast<uint8_t *>(base);
+    size_t off = 0;
+    const auto take = [&](size_t sz) -> void * {
+        void *p = b ? b + off : nullptr;
+        off += ro_align(sz);
+        return p;
+    };
+    RoScratch s;
+    s.ctr = static_cast<uint32_t *>(take(256));
+    s.runCnt = static_cast<uint32_t *>(take(4ull * T));                  // up to here: ro_zero_bytes
+    s.runBase = static_cast<uint32_t *>(take(4ull * T));
+    s.active = static_cast<uint32_t *>(take(4ull * T));
+    s.bucket = static_cast<unsigned long long *>(take(8ull * kRoBucket * T));
+    s.recs = static_cast<RoRec *>(take(16ull * n));
+    s.runs = static_cast<RoRun *>(take(16ull * n));
+    s.placed = static_cast<unsigned long long *>(take(8ull * n));
+    s.sortTmp = static_cast<unsigned long long *>(take(16ull * n));
+    s.ovMask = static_cast<unsigned long long *>(take(8ull * ((n + 63) / 64)));
+    if (bytes) *bytes = off;
+    return s;
+}
 inline size_t ro_scratch_bytes(uint32_t n, uint32_t T)
 {
-    return ro_zero_bytes(T) + 2 * ro_align(4ull * T) + ro_align(8ull * kRoBucket * T) + ro_align(16ull * n) +
-           ro_align(16ull * n) + ro_align(8ull * n) + ro_align(16ull * n) + ro_align(8ull * ((n + 63) / 64));
-}
-inline RoScratch ro_scratch_layout(void *base, uint32_t n, uint32_t T)
-{
-    uint8_t *b = static_cast<uint8_t *>(base);
-    RoScratch s;
-    s.ctr = reinterpret_cast<uint32_t *>(b);
-    s.runCnt = reinterpret_cast<uint32_t *>(b + 256);
-    b += ro_zero_bytes(T);
-    s.runBase = reinterpret_cast<uint32_t *>(b);
-    s.active = reinterpret_cast<uint32_t *>(b + ro_align(4ull * T));
-    b += 2 * ro_align(4ull * T);
-    s.bucket = reinterpret_cast<unsigned long long *>(b);
-    b += ro_align(8ull * kRoBucket * T);
-    s.recs = reinterpret_cast<RoRec *>(b);
-    b += ro_align(16ull * n);
-    s.runs = reinterpret_cast<RoRun *>(b);
-    b += ro_align(16ull * n);
-    s.placed = reinterpret_cast<unsigned long long *>(b);
-    b += ro_align(8ull * n);
-    s.sortTmp = reinterpret_cast<unsigned long long *>(b);
-    b += ro_align(16ull * n);
-    s.ovMask = reinterpret_cast<unsigned long long *>(b);
-    return s;
+    size_t bytes;
+    ro_scratch_layout(nullptr, n, T, &bytes);
+    return bytes;
 }
 hipError_t launch_ro_classify(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
                               uint32_t n, uint64_t now, void *work, void *scratch, size_t scratchBytes,
@@ -293,7 +305,6 @@ hipError_t launch_route_append(const uint8_t *pkts, uint32_t stride, const uint3
                                uint32_t cap, uint32_t *running, hipStream_t stream);
 hipError_t launch_route(const uint8_t *pkts, uint32_t stride, const uint32_t *lens, uint32_t n, int withLB,
                         uint32_t world, uint32_t self, int excludeSelf, uint8_t *out, uint32_t *outLens,
-                        uint32_t *counts, void *workspace, hipStream_t stream, uint32_t cap = 0,
-                        uint32_t *running = nullptr);   // cap > 0: append to per-rank regions of cap slots
+                        uint32_t *counts, void *workspace, hipStream_t stream);
 
 }  // namespace e2sar_amd

@@ -28,11 +28,10 @@ __global__ __launch_bounds__(kBlock) void emit_plan_kernel(EmitSrc S, EmitNum N,
                                                            e2sar_hip_seg_event *__restrict__ out,
                                                            uint32_t *__restrict__ counts)
 {
-    constexpr uint32_t kWaves = kBlock / 64;
-    __shared__ uint64_t waveNp[kWaves];
-    __shared__ uint32_t waveCut[kWaves], waveWhy[kWaves], waveUnits[kWaves], wavePk[kWaves];
+    constexpr int kWaves = kBlock / 64;
+    __shared__ uint64_t waveNp[kWaves], waveCut[kWaves];
+    __shared__ uint32_t waveUnits[kWaves], wavePk[kWaves];
     __shared__ uint32_t sAvail, sShort;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     if (threadIdx.x == 0) {
         uint32_t avail = maxEvents;
         if (S.count) {
@@ -58,51 +57,36 @@ __global__ __launch_bounds__(kBlock) void emit_plan_kernel(EmitSrc S, EmitNum N,
         const uint64_t off = S.pitch ? (uint64_t)i * S.pitch : active ? S.offsets[i] : 0ull;
         const bool inside = S.pitch ? bytes <= S.pitch : (off <= S.dataBytes && bytes <= S.dataBytes - off);
         const uint32_t np = (active && inside) ? bytes / maxPld + (bytes % maxPld != 0u) : 0u;
-        const uint64_t incNp = wave_incl_scan_shfl((uint64_t)np, lane);
-        if (lane == 63) waveNp[wv] = incNp;
-        __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t w = 0; w < wv; w++) before += waveNp[w];
-        const bool fails = active && (!inside || before + incNp > maxPackets);
-        const unsigned long long miss = __ballot(fails), outside = __ballot(active && !inside);
-        if (lane == 0) {
-            const uint32_t f = miss ? (uint32_t)__builtin_ctzll(miss) : 0u;
-            waveCut[wv] = miss ? b0 + wv * 64u + f : ~0u;
-            waveWhy[wv] = ((outside >> f) & 1ull) ? 2u : 1u;
-        }
-        __syncthreads();
-        uint32_t cut = ~0u, cutWhy = 0;
-        for (uint32_t w = 0; w < kWaves; w++)
-            if (waveCut[w] < cut) cut = waveCut[w], cutWhy = waveWhy[w];
+        uint64_t stepNp;
+        uint32_t stepUnits, stepPk;
+        const uint64_t before = carry + block_excl_scan<uint64_t, kWaves>((uint64_t)np, waveNp, stepNp);
+        const bool fails = active && (!inside || before + np > maxPackets);
+        // the first failing event and why it fails (2: outside its source, 1: no room), in one key
+        const uint64_t first = block_first<uint64_t, kWaves>(fails, ((uint64_t)i << 32) | (inside ? 1u : 2u), waveCut);
+        const uint32_t cut = (uint32_t)(first >> 32), cutWhy = (uint32_t)first;
         const bool taken = active && i < cut;
         const uint32_t nu = taken ? (uint32_t)(((uint64_t)np * spc + unitChunks - 1u) / unitChunks) : 0u;
-        const uint32_t incNu = wave_incl_scan_shfl(nu, lane);
-        const uint32_t incPk = wave_incl_scan_shfl(taken ? np : 0u, lane);
-        if (lane == 63) {
-            waveUnits[wv] = incNu;
-            wavePk[wv] = incPk;
-        }
+        const uint32_t incNu = block_scan_post(nu, waveUnits);       // two scans behind one barrier
+        block_scan_post(taken ? np : 0u, wavePk);
         __syncthreads();
+        const uint32_t firstUnit = units + block_scan_before<uint32_t, kWaves>(waveUnits, stepUnits) + incNu - nu;
+        block_scan_before<uint32_t, kWaves>(wavePk, stepPk);
         if (taken) {
-            uint32_t first = units;
-            for (uint32_t w = 0; w < wv; w++) first += waveUnits[w];
             const uint64_t tick = N.lbTickBase + (uint64_t)i * N.lbTickStep;
             e2sar_hip_seg_event d;
             d.data = S.data + off;
             d.eventNum = N.ticksAsEventNum ? tick : N.eventNums ? N.eventNums[i] : N.eventNumBase + i;
             d.lbTick = tick;
             d.bytes = bytes;
-            d.pktBase = (uint32_t)(before + incNp - np);     // every event in front of a taken one is taken
+            d.pktBase = (uint32_t)before;                    // every event in front of a taken one is taken
             d.dataId = (uint16_t)N.dataId;
             d.entropy = (uint16_t)(N.entropyBase + i);
-            d.reserved = first + incNu - nu;
+            d.reserved = firstUnit;
             out[i] = d;
         }
-        for (uint32_t w = 0; w < kWaves; w++) {
-            carry += waveNp[w];
-            units += waveUnits[w];
-            pk += wavePk[w];
-        }
+        carry += stepNp;
+        units += stepUnits;
+        pk += stepPk;
         if (cut != ~0u) {                                   // the same in every thread
             n = cut;
             why = cutWhy;

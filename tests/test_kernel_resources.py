@@ -23,8 +23,9 @@ KERNELS = {
     "zero_words_kernel": 1, "fill_bytes_kernel": 1, "copy_spans_kernel": 1, "reas_gc_kernel": 1,
     "reas_recycle_kernel": 1, "reas_compact_kernel": 1, "reas_compact_finish": 1, "relay_plan_kernel": 1,
     "route_hist_kernel": 1, "route_scan_kernel": 1, "route_pack_kernel": 1, "route_append_kernel": 1,
+    "collect_plan_kernel": 1, "collect_copy_kernel": 1, "emit_plan_kernel": 1, "seg_flat_kernel": 2,
 }
-assert sum(KERNELS.values()) == 33
+assert sum(KERNELS.values()) == 38
 
 
 def _remarks(src, tmp_path):
