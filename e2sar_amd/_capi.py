@@ -169,7 +169,6 @@ assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
 
 vp = C.c_void_p
-u8p = C.c_void_p
 i = C.c_int
 u32 = C.c_uint32
 u64 = C.c_uint64
@@ -269,12 +268,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `make` (or __graft_entry__.build()). "
                 "The E2SAR SAR path has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        for name, (res, args) in EXPERIMENTAL_SIGNATURES.items():
-            if hasattr(L, name):
+        for name, (res, args) in {**SIGNATURES, **EXPERIMENTAL_SIGNATURES}.items():
+            if name in SIGNATURES or hasattr(L, name):      # experimental forms: only where present
                 fn = getattr(L, name)
                 fn.restype = res
                 fn.argtypes = args

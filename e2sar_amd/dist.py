@@ -20,22 +20,80 @@ call pattern to mirror.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.distributed as dist
+
+from ._capi import lib
+from .sar import _call, _s
 
 
 def owner(event_num: int, world: int) -> int:
     return int(event_num) % int(world)
 
 
-def _via_host(group, t: torch.Tensor) -> bool:
+def _via_host(group) -> bool:
     """gloo's collectives take host tensors (device tensors are staged through host memory)
     and have no list all-to-all: with gloo every exchange goes through all_to_all_single on
     host tensors."""
     return dist.get_backend(group) == "gloo"
+
+
+# ---- the pieces of an exchange, stated once: exchange, exchange_regions and SpreadPipeline use them ----
+
+def _splits(m: List[List[int]], rank: int) -> Tuple[List[int], List[int]]:
+    """(send, recv) split sizes of `rank`: its row and its column of the count matrix."""
+    return m[rank], [row[rank] for row in m]
+
+
+def _any_sent(m: List[List[int]]) -> bool:
+    """False when no rank sends anything: every rank then skips the collective."""
+    return any(any(row) for row in m)
+
+
+def _check_cap(m: List[List[int]], cap: int) -> None:
+    if any(c > cap for row in m for c in row):
+        raise RuntimeError(f"route regions overflowed (cap {cap} datagrams per rank): {m}")
+
+
+def _recv_buffers(out, n_recv: int, stride: int, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`out` when it is on `dev` and holds n_recv datagrams, else new receive buffers."""
+    if out is not None and out[0].numel() >= n_recv * stride and out[1].numel() >= n_recv and out[0].device == dev:
+        return out
+    return (torch.empty(max(n_recv, 1) * stride, dtype=torch.uint8, device=dev),
+            torch.empty(max(n_recv, 1), dtype=torch.int32, device=dev))
+
+
+def _a2a_spans(rpk, rln, spk, sln, sc: List[int], rc: List[int], stride: int, group) -> None:
+    """The all_to_all_single pair (slots, lengths) over contiguous spans in rank order; with
+    gloo through host staging copies."""
+    def pair(rp, rl, sp, sl):
+        dist.all_to_all_single(rp, sp, [c * stride for c in rc], [c * stride for c in sc], group=group)
+        dist.all_to_all_single(rl, sl, rc, sc, group=group)
+
+    if not _via_host(group):
+        return pair(rpk, rln, spk, sln)
+    hpk, hln = torch.empty(rpk.numel(), dtype=torch.uint8), torch.empty(rln.numel(), dtype=torch.int32)
+    pair(hpk, hln, spk.cpu(), sln.cpu())
+    rpk.copy_(hpk)
+    rln.copy_(hln)
+
+
+def _a2a_regions(send_pk, send_ln, recv_pk, recv_ln, sc: List[int], rc: List[int], cap: int, stride: int, group):
+    """All-to-all of region views: the first sc[d] slots of region d (cap slots each) of the
+    send buffers go to rank d; what rank s sends lands at slot sum(rc[:s]) of the receive
+    buffers.  nccl: all_to_all over the views, no packing copy; gloo: the views are
+    gathered on the host and go through _a2a_spans."""
+    W = len(sc)
+    spk = [send_pk[d * cap * stride:(d * cap + sc[d]) * stride] for d in range(W)]
+    sln = [send_ln[d * cap:d * cap + sc[d]] for d in range(W)]
+    if _via_host(group):
+        return _a2a_spans(recv_pk[: sum(rc) * stride], recv_ln[: sum(rc)], torch.cat([v.cpu() for v in spk]),
+                          torch.cat([v.cpu() for v in sln]), sc, rc, stride, group)
+    roff = [sum(rc[:s]) for s in range(W)]
+    dist.all_to_all([recv_pk[roff[s] * stride:(roff[s] + rc[s]) * stride] for s in range(W)], spk, group=group)
+    dist.all_to_all([recv_ln[roff[s]:roff[s] + rc[s]] for s in range(W)], sln, group=group)
 
 
 def count_matrix(counts: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> List[List[int]]:
@@ -45,7 +103,7 @@ def count_matrix(counts: torch.Tensor, group: Optional[dist.ProcessGroup] = None
     if counts.numel() != world:
         raise ValueError("counts must have one entry per rank")
     c = counts.to(torch.int64)
-    if _via_host(group, c):
+    if _via_host(group):
         c = c.cpu()
     rows = [torch.empty_like(c) for _ in range(world)]
     dist.all_gather(rows, c, group=group)
@@ -54,9 +112,7 @@ def count_matrix(counts: torch.Tensor, group: Optional[dist.ProcessGroup] = None
 
 def exchange_counts(counts: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> Tuple[List[int], List[int]]:
     """(send, recv) split sizes of this rank (count_matrix's row and column)."""
-    m = count_matrix(counts, group)
-    rank = dist.get_rank(group)
-    return m[rank], [m[s][rank] for s in range(len(m))]
+    return _splits(count_matrix(counts, group), dist.get_rank(group))
 
 
 def exchange(send_pk: torch.Tensor, send_ln: torch.Tensor, counts: Union[Sequence[int], torch.Tensor], stride: int,
@@ -75,42 +131,25 @@ def exchange(send_pk: torch.Tensor, send_ln: torch.Tensor, counts: Union[Sequenc
     """
     world = dist.get_world_size(group)
     dev = send_pk.device
-    via_host = _via_host(group, send_pk)
     anything = True
     if isinstance(counts, torch.Tensor):
         m = count_matrix(counts, group)
-        rank = dist.get_rank(group)
-        sc, rc = m[rank], [m[s][rank] for s in range(world)]
-        anything = any(any(row) for row in m)
+        sc, rc = _splits(m, dist.get_rank(group))
+        anything = _any_sent(m)
     else:
         sc = [int(x) for x in counts]
         if len(sc) != world:
             raise ValueError("counts must have one entry per rank")
-        cdev = torch.device("cpu") if via_host else dev
-        cnt = torch.tensor(sc, dtype=torch.int64, device=cdev)
+        cnt = torch.tensor(sc, dtype=torch.int64, device=torch.device("cpu") if _via_host(group) else dev)
         rcnt = torch.empty_like(cnt)
         dist.all_to_all_single(rcnt, cnt, group=group)
         rc = [int(x) for x in rcnt.tolist()]
-    n_recv = sum(rc)
-    if out is not None and out[0].numel() >= n_recv * stride and out[1].numel() >= n_recv and out[0].device == dev:
-        recv_pk, recv_ln = out
-    else:
-        recv_pk = torch.empty(max(n_recv, 1) * stride, dtype=torch.uint8, device=dev)
-        recv_ln = torch.empty(max(n_recv, 1), dtype=torch.int32, device=dev)
-    n_send = sum(sc)
+    n_send, n_recv = sum(sc), sum(rc)
+    recv_pk, recv_ln = _recv_buffers(out, n_recv, stride, dev)
     if not anything:
-        return recv_pk, recv_ln, 0                          # no rank sends anything: skip the collective
-    spk, sln = send_pk[: n_send * stride], send_ln[:n_send]
-    rpk, rln = recv_pk[: n_recv * stride], recv_ln[:n_recv]
-    if via_host:
-        hpk, hln = torch.empty(n_recv * stride, dtype=torch.uint8), torch.empty(n_recv, dtype=torch.int32)
-        dist.all_to_all_single(hpk, spk.cpu(), [c * stride for c in rc], [c * stride for c in sc], group=group)
-        dist.all_to_all_single(hln, sln.cpu(), rc, sc, group=group)
-        rpk.copy_(hpk)
-        rln.copy_(hln)
-    else:
-        dist.all_to_all_single(rpk, spk, [c * stride for c in rc], [c * stride for c in sc], group=group)
-        dist.all_to_all_single(rln, sln, rc, sc, group=group)
+        return recv_pk, recv_ln, 0
+    _a2a_spans(recv_pk[: n_recv * stride], recv_ln[:n_recv], send_pk[: n_send * stride], send_ln[:n_send], sc, rc,
+               stride, group)
     return recv_pk, recv_ln, n_recv
 
 
@@ -125,114 +164,84 @@ def exchange_regions(send_pk: torch.Tensor, send_ln: torch.Tensor, running: torc
     gloo: the regions are gathered on the host and sent with all_to_all_single.  Returns
     (recv_pk, recv_ln, n_recv), received spans contiguous in source-rank order.  m: the
     count matrix when the caller already gathered it."""
-    world = dist.get_world_size(group)
-    rank = dist.get_rank(group)
     if m is None:
         m = count_matrix(running, group)
-    if any(c > cap for row in m for c in row):
-        raise RuntimeError(f"route regions overflowed (cap {cap} datagrams per rank): {m}")
-    sc, rc = m[rank], [m[s][rank] for s in range(world)]
+    _check_cap(m, cap)
+    sc, rc = _splits(m, dist.get_rank(group))
     n_recv = sum(rc)
-    dev = send_pk.device
-    if out is not None and out[0].numel() >= n_recv * stride and out[1].numel() >= n_recv and out[0].device == dev:
-        recv_pk, recv_ln = out
-    else:
-        recv_pk = torch.empty(max(n_recv, 1) * stride, dtype=torch.uint8, device=dev)
-        recv_ln = torch.empty(max(n_recv, 1), dtype=torch.int32, device=dev)
-    if not any(any(row) for row in m):
-        return recv_pk, recv_ln, 0                          # no rank sends anything: skip the collective
-    roff = [sum(rc[:s]) for s in range(world)]
-    if _via_host(group, send_pk):
-        spk = torch.cat([send_pk[d * cap * stride:(d * cap + sc[d]) * stride].cpu() for d in range(world)])
-        sln = torch.cat([send_ln[d * cap:d * cap + sc[d]].cpu() for d in range(world)])
-        hpk, hln = torch.empty(n_recv * stride, dtype=torch.uint8), torch.empty(n_recv, dtype=torch.int32)
-        dist.all_to_all_single(hpk, spk, [c * stride for c in rc], [c * stride for c in sc], group=group)
-        dist.all_to_all_single(hln, sln, rc, sc, group=group)
-        recv_pk[: n_recv * stride].copy_(hpk)
-        recv_ln[:n_recv].copy_(hln)
-    else:
-        dist.all_to_all([recv_pk[roff[s] * stride:(roff[s] + rc[s]) * stride] for s in range(world)],
-                        [send_pk[d * cap * stride:(d * cap + sc[d]) * stride] for d in range(world)], group=group)
-        dist.all_to_all([recv_ln[roff[s]:roff[s] + rc[s]] for s in range(world)],
-                        [send_ln[d * cap:d * cap + sc[d]] for d in range(world)], group=group)
+    recv_pk, recv_ln = _recv_buffers(out, n_recv, stride, send_pk.device)
+    if not _any_sent(m):
+        return recv_pk, recv_ln, 0
+    _a2a_regions(send_pk, send_ln, recv_pk, recv_ln, sc, rc, cap, stride, group)
     return recv_pk, recv_ln, n_recv
 
 
-class RegionRouter:
+class _Router:
+    """What both routers share: the send buffers of `slots` datagram slots, the per-rank
+    count vector, and the leading arguments of every e2sar_hip_route_* call."""
+
+    def __init__(self, ctx, stride: int, slots: int, max_batch: int, world: int, rank: int, with_lb_header: bool):
+        self.ctx, self.stride, self.world, self.rank = ctx, stride, world, rank
+        self.with_lb, self.max_batch = with_lb_header, max_batch
+        self.send_pk = torch.empty(slots * stride, dtype=torch.uint8, device=ctx.torch_device)
+        self.send_ln = torch.empty(slots, dtype=torch.int32, device=ctx.torch_device)
+
+    def _rank_counts(self) -> torch.Tensor:
+        return torch.zeros(self.world, dtype=torch.int32, device=self.ctx.torch_device)
+
+    def _checked_args(self, pk: torch.Tensor, ln: torch.Tensor, n: int) -> tuple:
+        """The arguments every e2sar_hip_route_* call begins with, for a batch the router was sized for."""
+        if n > self.max_batch:
+            raise ValueError("batch larger than the router was sized for")
+        return (self.ctx.handle, pk.data_ptr(), self.stride, ln.data_ptr(), n, 1 if self.with_lb else 0,
+                self.world, self.rank)
+
+
+class RegionRouter(_Router):
     """Routes a stream of landed batches, one launch per batch, into per-rank regions of
     cap datagram slots (e2sar_hip_route_append); ``exchange_regions`` sends them once per
     step.  Routing a batch right after it landed reads it from the Infinity Cache."""
 
     def __init__(self, ctx, stride: int, cap: int, max_batch: int, world: int, rank: int,
                  with_lb_header: bool = True, foreign_only: bool = True):
-        from ._capi import lib
-        self.ctx = ctx
-        self.stride, self.cap, self.world, self.rank = stride, cap, world, rank
-        self.with_lb, self.foreign_only, self.max_batch = with_lb_header, foreign_only, max_batch
-        d = ctx.torch_device
-        self.send_pk = torch.empty(world * cap * stride, dtype=torch.uint8, device=d)
-        self.send_ln = torch.empty(world * cap, dtype=torch.int32, device=d)
-        self.running = torch.zeros(world, dtype=torch.int32, device=d)
-        ws = int(lib().e2sar_hip_route_workspace_bytes(max_batch, world))
-        self.workspace = torch.empty(max(ws, 16), dtype=torch.uint8, device=d)
+        super().__init__(ctx, stride, world * cap, max_batch, world, rank, with_lb_header)
+        self.cap, self.foreign_only = cap, foreign_only
+        self.running = self._rank_counts()    # datagrams appended to each region since reset()
 
     def reset(self, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Empty the regions (a fill kernel on the stream, default the current one: capture-safe)."""
-        from ._capi import check, lib
-        from .sar import _stream_handle
-        check(lib().e2sar_hip_memset_async(self.ctx.handle, C.c_void_p(self.running.data_ptr()), 0,
-                                           self.running.numel() * 4, C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_memset_async", self.ctx.handle, self.running.data_ptr(), 0, self.running.numel() * 4,
+              _s(stream))
 
     def route(self, pk: torch.Tensor, ln: torch.Tensor, n: int, stream: Optional[torch.cuda.Stream] = None):
-        from ._capi import check, lib
-        from .sar import _stream_handle
-        if n > self.max_batch:
-            raise ValueError("batch larger than the router was sized for")
-        check(lib().e2sar_hip_route_append(
-            self.ctx.handle, C.c_void_p(pk.data_ptr()), self.stride, C.c_void_p(ln.data_ptr()), n,
-            1 if self.with_lb else 0, self.world, self.rank, 1 if self.foreign_only else 0,
-            C.c_void_p(self.send_pk.data_ptr()), C.c_void_p(self.send_ln.data_ptr()), self.cap,
-            C.c_void_p(self.running.data_ptr()), C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
-            C.c_void_p(_stream_handle(stream))))
+        # the workspace pair is unused by e2sar_hip_route_append (e2sar_hip.h): NULL / 0
+        _call("e2sar_hip_route_append", *self._checked_args(pk, ln, n), 1 if self.foreign_only else 0,
+              self.send_pk.data_ptr(), self.send_ln.data_ptr(), self.cap, self.running.data_ptr(), None, 0,
+              _s(stream))
 
     def exchange(self, group: Optional[dist.ProcessGroup] = None,
                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         return exchange_regions(self.send_pk, self.send_ln, self.running, self.cap, self.stride, group, out)
 
 
-class PacketRouter:
+class PacketRouter(_Router):
     """Packs a landed datagram batch into per-owner spans on the GPU."""
 
     def __init__(self, ctx, stride: int, max_packets: int, world: int, rank: int, with_lb_header: bool = True):
-        from ._capi import lib
-        self.ctx = ctx
-        self.stride = stride
-        self.world = world
-        self.rank = rank
-        self.with_lb = with_lb_header
-        self.max_packets = max_packets
-        d = ctx.torch_device
-        self.send_pk = torch.empty(max(max_packets, 1) * stride, dtype=torch.uint8, device=d)
-        self.send_ln = torch.empty(max(max_packets, 1), dtype=torch.int32, device=d)
-        self.counts = torch.zeros(world, dtype=torch.int32, device=d)
+        super().__init__(ctx, stride, max(max_packets, 1), max_packets, world, rank, with_lb_header)
+        self.max_packets = max_packets        # the name this router's size has always had: max_batch
+        self.counts = self._rank_counts()
         ws = int(lib().e2sar_hip_route_workspace_bytes(max_packets, world))
-        self.workspace = torch.empty(max(ws, 16), dtype=torch.uint8, device=d)
+        self.workspace = torch.empty(max(ws, 16), dtype=torch.uint8, device=ctx.torch_device)
 
     def route(self, pk: torch.Tensor, ln: torch.Tensor, n: int, stream: Optional[torch.cuda.Stream] = None,
               foreign_only: bool = False):
         """Returns (send_pk, send_ln, counts) with counts still on the device.  foreign_only:
         pack only datagrams other ranks own (e2sar_hip_route_foreign); the rest stay for a
         reassembler set to this rank's ownership."""
-        from ._capi import check, lib
-        from .sar import _stream_handle
-        if n > self.max_packets:
-            raise ValueError("batch larger than the router was sized for")
-        fn = lib().e2sar_hip_route_foreign if foreign_only else lib().e2sar_hip_route_batch
-        check(fn(
-            self.ctx.handle, C.c_void_p(pk.data_ptr()), self.stride, C.c_void_p(ln.data_ptr()), n,
-            1 if self.with_lb else 0, self.world, self.rank, C.c_void_p(self.send_pk.data_ptr()),
-            C.c_void_p(self.send_ln.data_ptr()), C.c_void_p(self.counts.data_ptr()),
-            C.c_void_p(self.workspace.data_ptr()), self.workspace.numel(), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_route_foreign" if foreign_only else "e2sar_hip_route_batch", *self._checked_args(pk, ln, n),
+              self.send_pk.data_ptr(), self.send_ln.data_ptr(), self.counts.data_ptr(), self.workspace.data_ptr(),
+              self.workspace.numel(), _s(stream))
         return self.send_pk, self.send_ln, self.counts
 
 
@@ -356,9 +365,8 @@ class SpreadPipeline:
         self.pending.append(slot)
 
     def _counts(self, m: List[List[int]]):
-        if any(c > self.max_batch for row in m for c in row):
-            raise RuntimeError(f"route regions overflowed (cap {self.max_batch} datagrams per rank): {m}")
-        sc, rc = m[self.rank], [m[s][self.rank] for s in range(self.world)]
+        _check_cap(m, self.max_batch)
+        sc, rc = _splits(m, self.rank)
         self.sent += sum(c for d, c in enumerate(sc) if d != self.rank)
         self.received += sum(c for s, c in enumerate(rc) if s != self.rank)
         self.matrices.append(m)
@@ -377,19 +385,11 @@ class SpreadPipeline:
         router = self.routers[slot]
         rpk, rln = self.recv[slot]
         n_recv = sum(rc)
-        st = self.stride
-        cap = self.max_batch
-        roff = [sum(rc[:s]) for s in range(W)]
         with torch.cuda.stream(self.comm):
             self.comm.wait_event(self.ev_rx[slot])       # the receive set's last reassembly has read it
-            if any(any(row) for row in m):
-                def a2a(stream=None):
-                    dist.all_to_all([rpk[roff[s] * st:(roff[s] + rc[s]) * st] for s in range(W)],
-                                    [router.send_pk[d * cap * st:(d * cap + sc[d]) * st] for d in range(W)],
-                                    group=self.group)
-                    dist.all_to_all([rln[roff[s]:roff[s] + rc[s]] for s in range(W)],
-                                    [router.send_ln[d * cap:d * cap + sc[d]] for d in range(W)], group=self.group)
-                self.timed("exchange", self.comm, a2a)
+            if _any_sent(m):
+                self.timed("exchange", self.comm, lambda stream=None: _a2a_regions(
+                    router.send_pk, router.send_ln, rpk, rln, sc, rc, self.max_batch, self.stride, self.group))
             self.ev_a2a[slot].record(self.comm)
         self.recv_log.append((slot, n_recv))
         if n_recv:
@@ -406,12 +406,10 @@ class SpreadPipeline:
         router = self.routers[slot]
         m = count_matrix(router.running, self.group)
         self._counts(m)
-        res = []
-
-        def ex(stream=None):
-            res.append(exchange_regions(router.send_pk, router.send_ln, router.running, self.max_batch,
-                                        self.stride, self.group, out=self.recv[slot], m=m))
-        self.timed("exchange", main, ex)
+        res = []                # collected here: the timed hook need not return what fn returns
+        self.timed("exchange", main, lambda stream=None: res.append(exchange_regions(
+            router.send_pk, router.send_ln, router.running, self.max_batch, self.stride, self.group,
+            out=self.recv[slot], m=m)))
         rpk, rln, n = res[0]
         self.recv_log.append((slot, n))
         if n:

@@ -2,8 +2,12 @@
 
 ``DeviceSegmenter`` and ``DeviceReassembler`` are thin, allocation-aware wrappers: event
 bytes, datagrams and reassembled events stay in HBM; torch is used only as the device
-memory / stream plumbing.  The reference-shaped ``Segmenter``/``Reassembler`` classes
-(``e2sar_amd.dataplane``) are built on top of these.
+memory / stream plumbing.  The reference-shaped ``Segmenter``/``Reassembler`` classes live in
+the pybind module ``e2sar_amd.e2sar_py``, over the C++ facade on the same C ABI.
+
+Every status-returning C-ABI call goes through ``_call``; its arguments are plain values
+(``_capi.SIGNATURES`` declares the argtypes): ``t.data_ptr()``, ``_p(t)`` where a tensor may
+be omitted, ``_s(stream)`` for the stream.
 """
 from __future__ import annotations
 
@@ -22,6 +26,67 @@ def _stream_handle(stream: Optional[torch.cuda.Stream]) -> int:
     if stream is None:
         stream = torch.cuda.current_stream()
     return int(stream.cuda_stream)
+
+
+_s = _stream_handle        # the short form the call sites use
+
+
+def _p(t: Optional[torch.Tensor]) -> int:
+    """Device address of an optional tensor: NULL when it is omitted."""
+    return t.data_ptr() if t is not None else 0
+
+
+def _call(name: str, *args) -> int:
+    """One C-ABI call by name; a negative status raises E2SARHipError."""
+    return check(getattr(lib(), name)(*args))
+
+
+class _Handle:
+    """Owner of one C-ABI object: ``_h`` (a c_void_p) is destroyed once, by close() or
+    when the owner is collected."""
+    _destroy: str
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# e2sar_hip_seg_event, as DeviceSegmenter.emit and DeviceReassembler.relay_plan write it
+SEG_EVENT = np.dtype(_capi.SegEvent)
+SEG_EVENT_BYTES = SEG_EVENT.itemsize
+# e2sar_hip_collect_rec: one event DeviceReassembler.collect delivered, and where in `out`
+COLLECT_REC = np.dtype(_capi.CollectRec)
+COLLECT_REC_BYTES = COLLECT_REC.itemsize
+
+
+def _parse(table: torch.Tensor, counts: torch.Tensor, rec: np.dtype) -> np.ndarray:
+    torch.cuda.synchronize(table.device)
+    n = int(counts[0].item())
+    raw = table[: n * rec.itemsize].cpu().numpy().tobytes()
+    return np.frombuffer(raw, rec).copy()
+
+
+def parse_emit(events: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
+    """The descriptors DeviceSegmenter.emit wrote, on the host: waits for the device, copies
+    the table and the counts, and returns a SEG_EVENT array of the n taken events."""
+    return _parse(events, counts, SEG_EVENT)
+
+
+def parse_collect(index: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
+    """The rows DeviceReassembler.collect wrote, on the host: waits for the device, copies
+    the index and the counts, and returns a COLLECT_REC array of the n taken events."""
+    return _parse(index, counts, COLLECT_REC)
 
 
 def total_hdr_len(use_ipv6: bool = False) -> int:
@@ -43,8 +108,9 @@ def packet_stride(max_pld: int) -> int:
     return int(lib().e2sar_hip_packet_stride(max_pld))
 
 
-class Context:
+class Context(_Handle):
     """A device + stream binding (e2sar_hip_ctx)."""
+    _destroy = "e2sar_hip_ctx_destroy"
 
     def __init__(self, device: int = 0, stream: Optional[torch.cuda.Stream] = None):
         torch.cuda.set_device(device)
@@ -52,15 +118,11 @@ class Context:
         self.torch_device = torch.device("cuda", device)
         self.stream = stream if stream is not None else torch.cuda.current_stream(device)
         h = C.c_void_p()
-        check(lib().e2sar_hip_ctx_create(device, C.c_void_p(int(self.stream.cuda_stream)), C.byref(h)))
+        _call("e2sar_hip_ctx_create", device, _s(self.stream), C.byref(h))
         self._h = h
 
-    @property
-    def handle(self) -> C.c_void_p:
-        return self._h
-
     def sync(self) -> None:
-        check(lib().e2sar_hip_ctx_sync(self._h))
+        _call("e2sar_hip_ctx_sync", self._h)
 
     def copy_spans(self, spans: Sequence[tuple], stream: Optional[torch.cuda.Stream] = None) -> None:
         """(src_ptr, dst_ptr, nbytes) spans, device or pinned host memory, copied by
@@ -68,18 +130,7 @@ class Context:
         arr = (_capi.CopySpan * max(1, len(spans)))()
         for k, (a, b, n) in enumerate(spans):
             arr[k] = _capi.CopySpan(int(a), int(b), int(n))
-        check(lib().e2sar_hip_copy_spans(self._h, arr, len(spans), C.c_void_p(_stream_handle(stream))))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().e2sar_hip_ctx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        _call("e2sar_hip_copy_spans", self._h, arr, len(spans), _s(stream))
 
 
 @dataclass
@@ -112,6 +163,10 @@ class DeviceSegmenter:
         self.stride = packet_stride(self.max_pld)
         self.lb_hdr_version = lb_hdr_version
 
+    def _need_slots(self, n: int, packets: torch.Tensor, *lens: torch.Tensor) -> None:
+        if packets.numel() < n * self.stride or any(ln.numel() < n for ln in lens):
+            raise ValueError("packet buffer too small")
+
     def plan(self, events: Sequence[tuple]) -> SegPlan:
         """events: (data_ptr, nbytes, eventNum, dataId, entropy, lbTick) tuples, data on device."""
         n = len(events)
@@ -130,7 +185,7 @@ class DeviceSegmenter:
             aligned4 = aligned4 and (int(ptr) % 4 == 0)
         tot = C.c_uint32()
         mx = C.c_uint32()
-        check(lib().e2sar_hip_seg_plan(arr, n, self.max_pld, C.byref(tot), C.byref(mx)))
+        _call("e2sar_hip_seg_plan", arr, n, self.max_pld, C.byref(tot), C.byref(mx))
         raw = np.frombuffer(bytes(arr)[: n * C.sizeof(_capi.SegEvent)], dtype=np.uint8).copy()
         dev = torch.from_numpy(raw).to(self.ctx.torch_device, non_blocking=False)
         return SegPlan(arr, dev, n, int(tot.value), int(mx.value), aligned4)
@@ -145,8 +200,8 @@ class DeviceSegmenter:
         starts = (C.c_uint32 * cap)()
         ng = C.c_uint32()
         _capi.need_experimental("DeviceSegmenter.groups")
-        check(lib().e2sar_hip_seg_groups(plan.host, plan.n_events, plan.max_packets_per_event, self.max_pld,
-                                         self.stride, starts, cap, C.byref(ng)))
+        _call("e2sar_hip_seg_groups", plan.host, plan.n_events, plan.max_packets_per_event, self.max_pld,
+              self.stride, starts, cap, C.byref(ng))
         if ng.value == 0:
             return None, 0
         host = np.frombuffer(bytes(starts), dtype=np.uint32)[: ng.value + 1].copy()
@@ -162,17 +217,14 @@ class DeviceSegmenter:
                 force: bool = False) -> int:
         """recycle: also recycle that reassembler (as DeviceReassembler.recycle(force)) in the
         same launch (e2sar_hip_segment_batch_recycle)."""
-        if packets.numel() < plan.total_packets * self.stride:
-            raise ValueError("packet buffer too small")
-        common = (C.c_void_p(plan.device.data_ptr()), plan.n_events,
-                  plan.max_packets_per_event, self.lb_hdr_version, self.max_pld,
-                  1 if plan.aligned4 else 0, C.c_void_p(packets.data_ptr()), self.stride,
-                  C.c_void_p(lens.data_ptr() if lens is not None else 0))
+        self._need_slots(plan.total_packets, packets)
+        batch = (self.ctx.handle, plan.device.data_ptr(), plan.n_events, plan.max_packets_per_event,
+                 self.lb_hdr_version, self.max_pld, 1 if plan.aligned4 else 0, packets.data_ptr(), self.stride,
+                 _p(lens))
         if recycle is not None:
-            check(lib().e2sar_hip_segment_batch_recycle(self.ctx.handle, *common, recycle.handle, 1 if force else 0,
-                                                        C.c_void_p(_stream_handle(stream))))
+            _call("e2sar_hip_segment_batch_recycle", *batch, recycle.handle, 1 if force else 0, _s(stream))
         else:
-            check(lib().e2sar_hip_segment_batch(self.ctx.handle, *common, C.c_void_p(_stream_handle(stream))))
+            _call("e2sar_hip_segment_batch", *batch, _s(stream))
         return plan.total_packets
 
     def segment_reassemble(self, plan: SegPlan, packets: torch.Tensor, lens: torch.Tensor,
@@ -180,13 +232,11 @@ class DeviceSegmenter:
                            stream: Optional[torch.cuda.Stream] = None) -> int:
         """Chained form: segment the batch and reassemble the same datagrams into `reas`
         in one launch (e2sar_hip_segment_reassemble_batch)."""
-        if packets.numel() < plan.total_packets * self.stride or lens.numel() < plan.total_packets:
-            raise ValueError("packet buffer too small")
+        self._need_slots(plan.total_packets, packets, lens)
         _capi.need_experimental("DeviceSegmenter.segment_reassemble")
-        check(lib().e2sar_hip_segment_reassemble_batch(
-            self.ctx.handle, C.c_void_p(plan.device.data_ptr()), plan.n_events, plan.max_packets_per_event,
-            plan.total_packets, self.lb_hdr_version, self.max_pld, C.c_void_p(packets.data_ptr()), self.stride,
-            C.c_void_p(lens.data_ptr()), reas._h, int(now_ms), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_segment_reassemble_batch", self.ctx.handle, plan.device.data_ptr(), plan.n_events,
+              plan.max_packets_per_event, plan.total_packets, self.lb_hdr_version, self.max_pld, packets.data_ptr(),
+              self.stride, lens.data_ptr(), reas._h, int(now_ms), _s(stream))
         return plan.total_packets
 
     def segment_reassemble_batches(self, plans: Sequence[SegPlan], bufs: Sequence[tuple],
@@ -196,14 +246,12 @@ class DeviceSegmenter:
         e2sar_hip_segment_reassemble_batches); bufs[k] = (packets, lens) of plans[k], all distinct."""
         arr = (_capi.SegReasBatch * max(1, len(plans)))()
         for k, (p, (pk, ln)) in enumerate(zip(plans, bufs)):
-            if pk.numel() < p.total_packets * self.stride or ln.numel() < p.total_packets:
-                raise ValueError("packet buffer too small")
+            self._need_slots(p.total_packets, pk, ln)
             arr[k] = _capi.SegReasBatch(p.device.data_ptr(), pk.data_ptr(), ln.data_ptr(), p.n_events,
                                         p.max_packets_per_event, p.total_packets, 0)
         _capi.need_experimental("DeviceSegmenter.segment_reassemble_batches")
-        check(lib().e2sar_hip_segment_reassemble_batches(
-            self.ctx.handle, arr, len(plans), self.lb_hdr_version, self.max_pld, self.stride, reas._h, int(now_ms),
-            C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_segment_reassemble_batches", self.ctx.handle, arr, len(plans), self.lb_hdr_version,
+              self.max_pld, self.stride, reas._h, int(now_ms), _s(stream))
         return sum(p.total_packets for p in plans)
 
     def segment_device(self, events: torch.Tensor, counts: torch.Tensor, max_events: int,
@@ -213,11 +261,9 @@ class DeviceSegmenter:
         the event count is counts[0], read by the kernel; max_events bounds it."""
         if packets.numel() < max_events * max_packets_per_event * self.stride:
             raise ValueError("packet buffer too small for the bound")
-        check(lib().e2sar_hip_segment_batch_dev(
-            self.ctx.handle, C.c_void_p(events.data_ptr()), C.c_void_p(counts.data_ptr()), max_events,
-            max_packets_per_event, self.lb_hdr_version, self.max_pld, C.c_void_p(packets.data_ptr()),
-            self.stride, C.c_void_p(lens.data_ptr() if lens is not None else 0),
-            C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_segment_batch_dev", self.ctx.handle, events.data_ptr(), counts.data_ptr(), max_events,
+              max_packets_per_event, self.lb_hdr_version, self.max_pld, packets.data_ptr(), self.stride, _p(lens),
+              _s(stream))
 
     def emit(self, data: torch.Tensor, lengths: torch.Tensor, packets: torch.Tensor, lens: Optional[torch.Tensor],
              events: torch.Tensor, counts: torch.Tensor, *, offsets: Optional[torch.Tensor] = None, pitch: int = 0,
@@ -253,16 +299,14 @@ class DeviceSegmenter:
                 or (offsets is not None and offsets.numel() < max_events)
                 or (event_nums is not None and event_nums.numel() < max_events)):
             raise ValueError("emit buffers too small for max_events")
-        ptr = lambda t: t.data_ptr() if t is not None else 0
-        src = _capi.SegSource(ptr(data), data.numel(), ptr(lengths), ptr(count), ptr(offsets), int(pitch),
+        src = _capi.SegSource(_p(data), data.numel(), _p(lengths), _p(count), _p(offsets), int(pitch),
                               min(int(max_event_bytes), 0xFFFFFFFF))
-        num = _capi.SegNumbering(ptr(event_nums), int(event_num_base) & (2**64 - 1), int(lb_tick_base) & (2**64 - 1),
+        num = _capi.SegNumbering(_p(event_nums), int(event_num_base) & (2**64 - 1), int(lb_tick_base) & (2**64 - 1),
                                  int(lb_tick_step) & (2**64 - 1), int(data_id) & 0xFFFF, int(entropy_base) & 0xFFFF,
                                  _capi.SEG_TICKS_AS_EVENTNUM if ticks_as_event_num else 0)
-        check(lib().e2sar_hip_seg_emit(
-            self.ctx.handle, C.byref(src), C.byref(num), max_events, self.lb_hdr_version, self.max_pld,
-            C.c_void_p(packets.data_ptr()), self.stride, max_packets, C.c_void_p(ptr(lens)),
-            C.c_void_p(events.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_seg_emit", self.ctx.handle, C.byref(src), C.byref(num), max_events, self.lb_hdr_version,
+              self.max_pld, packets.data_ptr(), self.stride, max_packets, _p(lens), events.data_ptr(),
+              counts.data_ptr(), _s(stream))
 
     def emit_rows(self, rows: torch.Tensor, lengths: torch.Tensor, count: Optional[torch.Tensor] = None,
                   stream: Optional[torch.cuda.Stream] = None, **numbering):
@@ -283,44 +327,18 @@ class DeviceSegmenter:
         return packets, lens, events, counts
 
 
-SEG_EVENT_BYTES = 40       # sizeof(e2sar_hip_seg_event)
-# e2sar_hip_seg_event, as DeviceSegmenter.emit and DeviceReassembler.relay_plan write it
-SEG_EVENT = np.dtype([("data", "<u8"), ("eventNum", "<u8"), ("lbTick", "<u8"), ("bytes", "<u4"), ("pktBase", "<u4"),
-                      ("dataId", "<u2"), ("entropy", "<u2"), ("reserved", "<u4")])
-assert SEG_EVENT.itemsize == SEG_EVENT_BYTES
+def _need_batch(what: str, n: int, stride: int, packets: torch.Tensor, *lens: torch.Tensor) -> None:
+    if any(ln.numel() < n for ln in lens) or packets.numel() < n * stride:
+        raise ValueError(what)
 
 
-def parse_emit(events: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
-    """The descriptors DeviceSegmenter.emit wrote, on the host: waits for the device, copies
-    the table and the counts, and returns a SEG_EVENT array of the n taken events."""
-    torch.cuda.synchronize(events.device)
-    n = int(counts[0].item())
-    raw = events[: n * SEG_EVENT_BYTES].cpu().numpy().tobytes()
-    return np.frombuffer(raw, SEG_EVENT).copy()
-
-
-# e2sar_hip_collect_rec: one event DeviceReassembler.collect delivered, and where in `out`
-COLLECT_REC = np.dtype([("eventNum", "<u8"), ("outOffset", "<u8"), ("bytes", "<u4"), ("dataId", "<u2"),
-                        ("flags", "<u2"), ("numFragments", "<u4"), ("reserved", "<u4")])
-COLLECT_REC_BYTES = COLLECT_REC.itemsize
-assert COLLECT_REC_BYTES == 32
-
-
-def parse_collect(index: torch.Tensor, counts: torch.Tensor) -> np.ndarray:
-    """The rows DeviceReassembler.collect wrote, on the host: waits for the device, copies
-    the index and the counts, and returns a COLLECT_REC array of the n taken events."""
-    torch.cuda.synchronize(index.device)
-    n = int(counts[0].item())
-    raw = index[: n * COLLECT_REC_BYTES].cpu().numpy().tobytes()
-    return np.frombuffer(raw, COLLECT_REC).copy()
-
-
-class DeviceReassembler:
+class DeviceReassembler(_Handle):
     """Reassembles device-resident datagram batches into a device event arena.
 
     Replaces the per-packet body of RecvThreadState::_threadBody
     (e2sarDPReassembler.cpp:310-428), the eventsInProgress map and the event queue.
     """
+    _destroy = "e2sar_hip_reas_destroy"
 
     def __init__(self, ctx: Context, with_lb_header: bool = False, table_slots: int = 4096,
                  queue_capacity: int = 4096, lost_capacity: int = 4096, arena_bytes: int = 1 << 30,
@@ -331,7 +349,7 @@ class DeviceReassembler:
         cfg = _capi.ReasConfig(1 if with_lb_header else 0, table_slots, queue_capacity,
                                lost_capacity, arena_bytes, flags, group_size)
         h = C.c_void_p()
-        check(lib().e2sar_hip_reas_create(ctx.handle, C.byref(cfg), C.byref(h)))
+        _call("e2sar_hip_reas_create", ctx.handle, C.byref(cfg), C.byref(h))
         self._h = h
         self.with_lb_header = with_lb_header
         self.arena_bytes = arena_bytes
@@ -339,27 +357,21 @@ class DeviceReassembler:
         self._evbuf = (_capi.EventRec * queue_capacity)()
         self._lostbuf = (_capi.LostRec * lost_capacity)()
 
-    @property
-    def handle(self):
-        return self._h
-
     def set_owner(self, world: int, rank: int) -> None:
         """Take only events with eventNum % world == rank (e2sar_hip_reas_set_owner)."""
-        check(lib().e2sar_hip_reas_set_owner(self._h, int(world), int(rank)))
+        _call("e2sar_hip_reas_set_owner", self._h, int(world), int(rank))
 
     def set_cold(self, cold: bool) -> None:
         """Streaming datagram loads for the following launches (e2sar_hip_reas_set_cold)."""
-        check(lib().e2sar_hip_reas_set_cold(self._h, 1 if cold else 0))
+        _call("e2sar_hip_reas_set_cold", self._h, 1 if cold else 0)
 
     def reassemble(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, n: int,
                    now_ms: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
         if n == 0:
             return
-        if lens.numel() < n or packets.numel() < n * stride:
-            raise ValueError("packet batch buffers too small")
-        check(lib().e2sar_hip_reassemble_batch(
-            self._h, C.c_void_p(packets.data_ptr()), stride, C.c_void_p(lens.data_ptr()), n,
-            int(now_ms), C.c_void_p(_stream_handle(stream))))
+        _need_batch("packet batch buffers too small", n, stride, packets, lens)
+        _call("e2sar_hip_reassemble_batch", self._h, packets.data_ptr(), stride, lens.data_ptr(), n, int(now_ms),
+              _s(stream))
 
     def reassemble_groups(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, n: int,
                           starts: Optional[torch.Tensor], n_groups: int, now_ms: int = 0,
@@ -368,15 +380,12 @@ class DeviceReassembler:
         was segmented in), e2sar_hip_reassemble_groups."""
         if n == 0:
             return
-        if lens.numel() < n or packets.numel() < n * stride:
-            raise ValueError("packet batch buffers too small")
+        _need_batch("packet batch buffers too small", n, stride, packets, lens)
         if starts is not None and starts.numel() < n_groups + 1:
             raise ValueError("group table too small")
         _capi.need_experimental("DeviceReassembler.reassemble_groups")
-        check(lib().e2sar_hip_reassemble_groups(
-            self._h, C.c_void_p(packets.data_ptr()), stride, C.c_void_p(lens.data_ptr()), n,
-            C.c_void_p(starts.data_ptr() if starts is not None else 0), n_groups if starts is not None else 0,
-            int(now_ms), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reassemble_groups", self._h, packets.data_ptr(), stride, lens.data_ptr(), n, _p(starts),
+              n_groups if starts is not None else 0, int(now_ms), _s(stream))
 
     def relay_plan(self, events: torch.Tensor, counts: torch.Tensor, first_record: int, max_events: int,
                    max_pld: int, lb_tick: int, entropy_base: int,
@@ -386,9 +395,8 @@ class DeviceReassembler:
         device tensor), without a host round trip (e2sar_hip_relay_plan)."""
         if events.numel() < max_events * SEG_EVENT_BYTES or counts.numel() < 2:
             raise ValueError("relay buffers too small")
-        check(lib().e2sar_hip_relay_plan(
-            self._h, first_record, max_events, max_pld, int(lb_tick), entropy_base & 0xFFFF,
-            C.c_void_p(events.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_relay_plan", self._h, first_record, max_events, max_pld, int(lb_tick),
+              entropy_base & 0xFFFF, events.data_ptr(), counts.data_ptr(), _s(stream))
 
     def collect(self, out: torch.Tensor, index: torch.Tensor, counts: torch.Tensor, first_record: int = 0,
                 max_events: Optional[int] = None, pitch: int = 0, align: int = 256,
@@ -406,9 +414,8 @@ class DeviceReassembler:
             max_events = index.numel() // COLLECT_REC_BYTES
         if index.numel() < max_events * COLLECT_REC_BYTES or counts.numel() < 4:
             raise ValueError("collect buffers too small")
-        check(lib().e2sar_hip_reas_collect(
-            self._h, first_record, max_events, C.c_void_p(out.data_ptr()), out.numel(), pitch, align,
-            C.c_void_p(index.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_collect", self._h, first_record, max_events, out.data_ptr(), out.numel(), pitch, align,
+              index.data_ptr(), counts.data_ptr(), _s(stream))
 
     def collect_rows(self, max_events: int, pitch: int, first_record: int = 0,
                      stream: Optional[torch.cuda.Stream] = None):
@@ -437,102 +444,80 @@ class DeviceReassembler:
                  now_ms: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
         if n == 0:
             return
-        if lens.numel() < n or packets.numel() < n * stride:
-            raise ValueError("packet batch buffers too small")
-        check(lib().e2sar_hip_reas_classify(
-            self._h, C.c_void_p(packets.data_ptr()), stride, C.c_void_p(lens.data_ptr()), n, int(now_ms),
-            C.c_void_p(work.data_ptr()), work.numel(), C.c_void_p(_stream_handle(stream))))
+        _need_batch("packet batch buffers too small", n, stride, packets, lens)
+        _call("e2sar_hip_reas_classify", self._h, packets.data_ptr(), stride, lens.data_ptr(), n, int(now_ms),
+              work.data_ptr(), work.numel(), _s(stream))
 
     def scatter(self, packets: torch.Tensor, stride: int, n: int, work: torch.Tensor,
                 stream: Optional[torch.cuda.Stream] = None) -> None:
         if n == 0:
             return
-        if packets.numel() < n * stride:
-            raise ValueError("packet batch buffer too small")
-        check(lib().e2sar_hip_reas_scatter(
-            self._h, C.c_void_p(packets.data_ptr()), stride, n, C.c_void_p(work.data_ptr()), work.numel(),
-            C.c_void_p(_stream_handle(stream))))
+        _need_batch("packet batch buffer too small", n, stride, packets)
+        _call("e2sar_hip_reas_scatter", self._h, packets.data_ptr(), stride, n, work.data_ptr(), work.numel(),
+              _s(stream))
 
     def scatter_classify(self, stride: int, s_packets: torch.Tensor, s_n: int, s_work: torch.Tensor,
                          c_packets: torch.Tensor, c_lens: torch.Tensor, c_n: int, c_work: torch.Tensor,
                          now_ms: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
         """One launch: scatter classified batch b while classifying batch b+1."""
-        if s_n and s_packets.numel() < s_n * stride:
-            raise ValueError("scatter batch buffer too small")
-        if c_n and (c_lens.numel() < c_n or c_packets.numel() < c_n * stride):
-            raise ValueError("classify batch buffers too small")
-        check(lib().e2sar_hip_reas_scatter_classify(
-            self._h, stride, C.c_void_p(s_packets.data_ptr()), s_n, C.c_void_p(s_work.data_ptr()), s_work.numel(),
-            C.c_void_p(c_packets.data_ptr()), C.c_void_p(c_lens.data_ptr()), c_n, int(now_ms),
-            C.c_void_p(c_work.data_ptr()), c_work.numel(), C.c_void_p(_stream_handle(stream))))
+        _need_batch("scatter batch buffer too small", s_n, stride, s_packets)
+        _need_batch("classify batch buffers too small", c_n, stride, c_packets, c_lens)
+        _call("e2sar_hip_reas_scatter_classify", self._h, stride, s_packets.data_ptr(), s_n, s_work.data_ptr(),
+              s_work.numel(), c_packets.data_ptr(), c_lens.data_ptr(), c_n, int(now_ms), c_work.data_ptr(),
+              c_work.numel(), _s(stream))
 
     def forget_stream(self, stream: torch.cuda.Stream) -> None:
         """Before the caller destroys `stream`, on which it launched through this reassembler:
         wait for it, stop tracking it and free its internal buffers
         (e2sar_hip_reas_forget_stream).  The stream must still be alive."""
-        check(lib().e2sar_hip_reas_forget_stream(self._h, C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_forget_stream", self._h, _s(stream))
 
     def gc(self, now_ms: int, timeout_ms: int, stream: Optional[torch.cuda.Stream] = None) -> None:
-        check(lib().e2sar_hip_reas_gc(self._h, int(now_ms), int(timeout_ms), C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_gc", self._h, int(now_ms), int(timeout_ms), _s(stream))
+
+    def _drain(self, name: str, buf: "C.Array") -> list:
+        """One poll call into `buf`; the records it returned, each copied out of the buffer."""
+        n = C.c_uint32()
+        _call(name, self._h, buf, len(buf), C.byref(n))
+        out = []
+        for k in range(n.value):
+            r = buf._type_()
+            C.memmove(C.byref(r), C.byref(buf[k]), C.sizeof(r))
+            out.append(r)
+        return out
 
     def poll(self) -> List[_capi.EventRec]:
-        n = C.c_uint32()
-        check(lib().e2sar_hip_reas_poll(self._h, self._evbuf, len(self._evbuf), C.byref(n)))
-        out = []
-        for k in range(n.value):
-            r = _capi.EventRec()
-            C.memmove(C.byref(r), C.byref(self._evbuf[k]), C.sizeof(r))
-            out.append(r)
-        return out
+        return self._drain("e2sar_hip_reas_poll", self._evbuf)
 
     def lost_poll(self) -> List[_capi.LostRec]:
-        n = C.c_uint32()
-        check(lib().e2sar_hip_reas_lost_poll(self._h, self._lostbuf, len(self._lostbuf), C.byref(n)))
-        out = []
-        for k in range(n.value):
-            r = _capi.LostRec()
-            C.memmove(C.byref(r), C.byref(self._lostbuf[k]), C.sizeof(r))
-            out.append(r)
-        return out
+        return self._drain("e2sar_hip_reas_lost_poll", self._lostbuf)
 
     def stats(self) -> _capi.ReasStats:
         s = _capi.ReasStats()
-        check(lib().e2sar_hip_reas_get_stats(self._h, C.byref(s)))
+        _call("e2sar_hip_reas_get_stats", self._h, C.byref(s))
         return s
 
     def recycle(self, force: bool = False, stream: Optional[torch.cuda.Stream] = None) -> None:
-        check(lib().e2sar_hip_reas_recycle(self._h, 1 if force else 0, C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_recycle", self._h, 1 if force else 0, _s(stream))
 
     def compact(self, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Move in-progress events to the alternate arena (see e2sar_hip_reas_compact)."""
-        check(lib().e2sar_hip_reas_compact(self._h, C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_compact", self._h, _s(stream))
         self.arena_ptr = int(lib().e2sar_hip_reas_arena(self._h) or 0)
 
     def reset_stats(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        check(lib().e2sar_hip_reas_reset_stats(self._h, C.c_void_p(_stream_handle(stream))))
+        _call("e2sar_hip_reas_reset_stats", self._h, _s(stream))
 
     def event_bytes(self, rec: _capi.EventRec) -> bytes:
         """Copy one reassembled event to host memory."""
         buf = (C.c_uint8 * max(rec.bytes, 1))()
         if rec.bytes:
-            check(lib().e2sar_hip_memcpy_d2h(self.ctx.handle, buf, C.c_void_p(self.arena_ptr + rec.arenaOffset),
-                                             rec.bytes))
+            _call("e2sar_hip_memcpy_d2h", self.ctx.handle, buf, self.arena_ptr + rec.arenaOffset, rec.bytes)
         return bytes(buf)[: rec.bytes]
 
     def arena_tensor(self) -> torch.Tensor:
         """Zero-copy uint8 view of the whole device arena."""
         return _device_view(self.arena_ptr, self.arena_bytes, self.ctx.torch_device)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().e2sar_hip_reas_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class _CudaArray:
