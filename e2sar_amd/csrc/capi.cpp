@@ -750,6 +750,39 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
     });
 }
 
+int e2sar_hip_reassemble_batch_dev(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride,
+                                   const uint32_t *d_lens, const uint32_t *d_count, uint32_t maxPackets,
+                                   uint64_t now_ms, void *stream)
+{
+    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
+    // NULL never means "all" here: a caller with a host count uses e2sar_hip_reassemble_batch
+    if (!d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (!d_count) return fail(E2SAR_HIP_ERR_PARAMETER, "d_count is NULL");
+    if (int st = check_batch(r, d_packets, stride, maxPackets)) return st;
+    if (ref_order(r))
+        return fail(E2SAR_HIP_ERR_LOGIC, "a REFERENCE_ORDER reassembler takes its datagram count from the host: its key, "
+                                         "place and walk launches are sized by it (use e2sar_hip_reassemble_batch)");
+    if (maxPackets == 0) return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "reassembly launch (device count)", [&](hipStream_t s) -> int {
+        // Everything the host decides, it decides from the bound: reassemble_batch's choice
+        // of form, cold_loads' of the scatter's loads, the work buffer of this stream.
+        if ((uint64_t)maxPackets * stride > kFusedMaxBytes) {
+            auto &sc = r->scratch[s];
+            if (int rc = grow(r, s, sc.work, work_bytes(maxPackets))) return rc;
+            void *work = sc.work.mem.get();
+            hipError_t e = launch_reas_classify_dev(r->dev, d_packets, stride, d_lens, d_count, maxPackets, now_ms, work, s);
+            if (e == hipSuccess)
+                e = launch_reas_scatter_dev(r->dev, d_packets, stride, d_count, maxPackets, work, s,
+                                            cold_loads(r, maxPackets, stride));
+            if (e != hipSuccess) return hip_fail(e, "reassembly launch (device count, split form)");
+            return E2SAR_HIP_OK;
+        }
+        const hipError_t e = launch_reassemble_dev(r->dev, d_packets, stride, d_lens, d_count, maxPackets, now_ms, s);
+        if (e != hipSuccess) return hip_fail(e, "reassembly launch (device count)");
+        return E2SAR_HIP_OK;
+    });
+}
+
 #if E2SAR_HIP_EXPERIMENTAL
 int e2sar_hip_seg_groups(const e2sar_hip_seg_event *events, uint32_t nEvents, uint32_t maxPacketsPerEvent,
                          uint32_t maxPldLen, uint32_t stride, uint32_t *starts, uint32_t cap, uint32_t *nGroups)

@@ -18,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_order, reas_upkeep, reas_collect, reas_build, seg_emit, route), all
+// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_order, reas_upkeep, reas_collect, reas_build, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -32,6 +32,7 @@
 #include "reas_store.hpp"
 #include "reas_fused.hpp"
 #include "reas_split.hpp"
+#include "reas_devcount.hpp"
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
 #include "reas_collect.hpp"
@@ -421,6 +422,27 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
     return hipGetLastError();
 }
 
+// launch_reassemble for a batch of min(*d_count, maxPackets) datagrams: the group size, the
+// grid and the kernel are those of a batch of maxPackets, the only number the host has.
+hipError_t launch_reassemble_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                                 const uint32_t *d_count, uint32_t maxPackets, uint64_t now, hipStream_t stream)
+{
+    constexpr int U = kReasU;
+    if (maxPackets == 0) return hipSuccess;
+    const bool small = reas_threads(stride) == kReasNTSmall;
+    const uint32_t G = reas_group_size(maxPackets, stride, R.groupSize, small ? reas_resident_groups<U, kReasNTSmall>
+                                                                              : reas_resident_groups<U, kReasNTJumbo>);
+    const uint32_t groups = cdiv(maxPackets, G);
+    if (small)
+        hipLaunchKernelGGL((reas_dev_kernel<U, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,
+                           pkts, stride, lens, d_count, maxPackets, now, G);
+    else
+        hipLaunchKernelGGL((reas_dev_kernel<U, kReasNTJumbo>), dim3(groups), dim3(kReasNTJumbo),
+                           occupancy_lds(reas_dev_kernel<U, kReasNTJumbo>, kReasJumboPerCU), stream, R,
+                           pkts, stride, lens, d_count, maxPackets, now, G);
+    return hipGetLastError();
+}
+
 #if E2SAR_HIP_EXPERIMENTAL
 hipError_t launch_reassemble_groups(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
                                     uint32_t n, const uint32_t *starts, uint32_t nGroups, uint64_t now,
@@ -521,6 +543,35 @@ hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t s
         const auto kernel = reas_scatter_kernel<V::U, V::NT, V::STAGE, V::TB>;
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
                            n, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
+    });
+    return hipGetLastError();
+}
+
+// The split form for a batch of min(*d_count, maxPackets) datagrams: grids, the scatter
+// group size and the work view are those of a batch of maxPackets.
+hipError_t launch_reas_classify_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                                    const uint32_t *d_count, uint32_t maxPackets, uint64_t now, void *work,
+                                    hipStream_t stream)
+{
+    if (maxPackets == 0) return hipSuccess;
+    const WorkView w = work_view(work, maxPackets);
+    hipLaunchKernelGGL(reas_classify_dev_kernel, dim3(cdiv(maxPackets, kBlock)), dim3(kBlock), 0, stream, R, pkts, stride,
+                       lens, d_count, maxPackets, now, w.info, w.fin);
+    return hipGetLastError();
+}
+
+hipError_t launch_reas_scatter_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *d_count,
+                                   uint32_t maxPackets, const void *work, hipStream_t stream, bool nt)
+{
+    if (maxPackets == 0) return hipSuccess;
+    const WorkView w = work_view(work, maxPackets);
+    uint32_t blocks = 0;
+    const uint32_t G = scatter_geometry(stride, maxPackets, blocks);
+    with_scatter_variant(stride, nt, [&](auto v) {
+        using V = decltype(v);
+        const auto kernel = reas_scatter_dev_kernel<V::U, V::NT, V::STAGE, V::TB>;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
+                           d_count, maxPackets, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
     });
     return hipGetLastError();
 }

@@ -383,6 +383,26 @@ class DeviceReassembler(_Handle):
         _call("e2sar_hip_reassemble_batch", self._h, packets.data_ptr(), stride, lens.data_ptr(), n, int(now_ms),
               _s(stream))
 
+    def reassemble_dev(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, count: torch.Tensor,
+                       max_packets: Optional[int] = None, now_ms: int = 0,
+                       stream: Optional[torch.cuda.Stream] = None) -> None:
+        """reassemble() of the first min(count[0], max_packets) datagrams, the count read by
+        the kernels (e2sar_hip_reassemble_batch_dev): no host read, capturable.  `count`: an
+        int32 device tensor (read as uint32) whose first element is the count -- a view such
+        as counts[1:2] of DeviceSegmenter.emit or of relay_plan.  max_packets bounds it and
+        sizes the launch; it defaults to what `packets` and `lens` hold."""
+        if count.dtype != torch.int32 or lens.dtype != torch.int32 or packets.dtype != torch.uint8:
+            raise ValueError("packets is a uint8 tensor, lens and count are int32 tensors")
+        if count.device != packets.device or lens.device != packets.device:
+            raise ValueError("packets, lens and count lie on one device")
+        if count.numel() < 1:
+            raise ValueError("count is empty")
+        if max_packets is None:
+            max_packets = min(lens.numel(), packets.numel() // stride)
+        _need_batch("packet batch buffers too small for max_packets", max_packets, stride, packets, lens)
+        _call("e2sar_hip_reassemble_batch_dev", self._h, packets.data_ptr(), stride, lens.data_ptr(), count.data_ptr(),
+              max_packets, int(now_ms), _s(stream))
+
     def reassemble_groups(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, n: int,
                           starts: Optional[torch.Tensor], n_groups: int, now_ms: int = 0,
                           stream: Optional[torch.cuda.Stream] = None) -> None:

@@ -264,6 +264,39 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
                                const uint32_t *d_lens, uint32_t nPackets, uint64_t now_ms,
                                void *stream);
 
+/* e2sar_hip_reassemble_batch for a batch whose datagram count lives on the device: the
+ * datagrams [0, n), n = min(*d_count, maxPackets), are reassembled, where *d_count is a
+ * device uint32 the kernels read when they run -- d_counts + 1 of e2sar_hip_seg_emit or of
+ * e2sar_hip_relay_plan, for instance.  The host never reads it, so a device-side
+ * segmentation feeds a reassembler without a wait, and the chain producer -> emit ->
+ * reassemble -> collect / build may be captured as one graph and replayed with another
+ * count each time.  Replaces the same per-packet body (e2sarDPReassembler.cpp:310-428).
+ *   No byte of a slot at or past n and no d_lens entry at or past n is read.  n == 0 changes
+ * nothing in the reassembler: no counter, no table slot, no arena byte.  Events, bytes,
+ * numFragments, every statistic and every lost record are those of
+ * e2sar_hip_reassemble_batch(..., n, ...) on the same datagrams, whenever that result does
+ * not depend on how a launch is cut into groups (offset 0 first, no duplicates: DESIGN.md
+ * 5.3) -- the groups here are cut for maxPackets, not for n.
+ *   All launch geometry comes from maxPackets: the group size (unless cfg.groupSize fixes
+ * it), the grid, the fused form or -- above 320 MiB of slots -- the split form, streaming
+ * loads for a batch that large, and the size and layout of the split form's internal work
+ * buffer (per stream, grown on first use, never inside a graph capture: LOGIC, as above).
+ * One kernel launch, two in the split form; after a stream's first use no allocation, no
+ * memset node, no wait: the call may be captured into a HIP graph.  A workgroup past n
+ * costs the load of one word.  set_owner, set_cold, the stream default and the waits of
+ * poll / lost_poll / get_stats are those of e2sar_hip_reassemble_batch.
+ *   Status: PARAMETER for a NULL r, d_packets, d_lens or d_count (NULL does not mean "all":
+ * a caller with a host count uses e2sar_hip_reassemble_batch); then the stride and batch
+ * checks of e2sar_hip_reassemble_batch, applied to maxPackets; LOGIC for a reassembler
+ * created with E2SAR_HIP_REAS_REFERENCE_ORDER -- that mode's key, place and walk launches
+ * and its scratch layout are sized by the datagram count, and giving them a device count
+ * means editing those kernels: not yet done.  maxPackets == 0 succeeds and launches
+ * nothing.  A failing call launches nothing.  Asynchronous on `stream` (NULL = the context
+ * stream). */
+int e2sar_hip_reassemble_batch_dev(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride,
+                                   const uint32_t *d_lens, const uint32_t *d_count,
+                                   uint32_t maxPackets, uint64_t now_ms, void *stream);
+
 /* The same work as e2sar_hip_reassemble_batch split in two phases so a caller can
  * pipeline batches: classify (headers only: validate, look up / create, count) writes
  * per-datagram destinations into d_work; scatter moves the payload bytes and publishes
