@@ -249,7 +249,10 @@ static void log_lost(e2o_reas *r, const item *it, int enqueLoss)
  *   - nbytes shorter than the headers: counted as badHeaderDiscards (reference reads
  *     past the datagram and memcpy's a negative length);
  *   - bufferOffset + payload > bufferLength: counted in dataErrCnt and dropped
- *     (reference overflows the heap buffer at :391).
+ *     (reference overflows the heap buffer at :391);
+ *   - bufferOffset + payload > the length of the item the fragment joins (an item created
+ *     by a fragment that announced a shorter bufferLength): counted in dataErrCnt and
+ *     dropped, numFragments and curBytes unchanged (reference overflows at :391 too).
  * Every other behaviour -- including the offset-0 "always new item" rule (:361-369),
  * duplicate double counting (:400) and eventSuccess on enqueue loss (:426) -- is kept.
  */
@@ -290,6 +293,9 @@ void e2o_reas_push(e2o_reas *r, const uint8_t *dgram, size_t nbytes)
         *slot = it;
         r->inProgress++;
     }
+
+    /* only an existing item reached at offset > 0 can be shorter than the fragment's own length */
+    if ((uint64_t)off + pl > it->bytes) { r->st.dataErrCnt++; return; }
 
     memcpy(it->event + off, re + 20, pl);        /* :391-392 */
     it->numFragments++;                          /* :398 */

@@ -76,6 +76,8 @@ def trace(s: Schedule) -> Trace:
                 if off == 0 or it is None:
                     it = items[key] = {"blen": blen, "cur": 0, "mask": np.zeros(blen, bool), "created": now,
                                        "frags": 0, "epochs": set()}
+                if off + pl > it["blen"]:
+                    continue              # overruns the item it joins: dropped (oracle's third guard)
                 it["cur"] += pl
                 it["frags"] += 1
                 it["mask"][off:off + pl] = True
