@@ -268,6 +268,23 @@ static int check_route(const e2sar_hip_ctx *ctx, uint32_t world, uint32_t self, 
     return E2SAR_HIP_OK;
 }
 
+// Where collect and build pack events: the output buffer's alignment; and the pitch of its
+// rows or cells and the alignment of its ragged events, `align` 0 becoming the default.  Two
+// checks, since the two entry points refuse in different orders.
+static int check_pack_out(const uint8_t *d_out)
+{
+    if (((uintptr_t)d_out & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "output buffer not 256-byte aligned");
+    return E2SAR_HIP_OK;
+}
+static int check_pack_layout(uint32_t pitch, uint32_t &align)
+{
+    if (pitch & 15u) return fail(E2SAR_HIP_ERR_PARAMETER, "pitch must be a multiple of 16");
+    if (align == 0) align = 256;
+    if (align < 16 || align > 4096 || (align & (align - 1)))
+        return fail(E2SAR_HIP_ERR_PARAMETER, "align must be 0 or a power of two in [16, 4096]");
+    return E2SAR_HIP_OK;
+}
+
 // reassemble_batch keeps the fused kernel up to this many bytes of datagram slots (a batch
 // that can still sit in the 256 MiB Infinity Cache) and switches to the split form above
 static constexpr uint64_t kFusedMaxBytes = 320ull << 20;
@@ -708,6 +725,45 @@ static hipError_t ro_classify(e2sar_hip_reas *r, hipStream_t s, const uint8_t *p
     return e;
 }
 
+// The launches of both reassembly entry points on stream s (caller holds r->mu): n
+// datagrams, or with d_count min(*d_count, n) of them, the count read by the kernels.
+// Everything the host decides, it decides from n: the form, the scatter's loads, the work
+// buffer of this stream.
+static int reassemble(e2sar_hip_reas *r, hipStream_t s, const uint8_t *d_packets, uint32_t stride, const uint32_t *d_lens,
+                      const uint32_t *d_count, uint32_t n, uint64_t now_ms)
+{
+    if (ref_order(r)) {                                   // host count only: the device-count entry point refuses
+        // classify in arrival order into the internal work buffer, then the scatter kernel
+        auto &sc = r->scratch[s];
+        if (int rc = ro_prepare(r, s, n)) return rc;
+        if (int rc = grow(r, s, sc.work, work_bytes(n))) return rc;
+        void *work = sc.work.mem.get();
+        hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, n, now_ms, work);
+        if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, n, work, s, cold_loads(r, n, stride));
+        if (e != hipSuccess) return hip_fail(e, "reference-order reassembly launch");
+        return E2SAR_HIP_OK;
+    }
+    // A batch whose datagrams cannot still be in the 256 MiB Infinity Cache (more than
+    // kFusedMaxBytes of slots) is read back from HBM whatever the caller did before, and
+    // there the split form -- classify, then one-round scatter workgroups with streaming
+    // loads -- is the faster one: 8 MiB events at MTU 9000, 70 per launch (65,730
+    // datagrams, BASELINE config 3): 1116 GiB/s fused vs 1302 split.  Internal work buffer
+    // of this stream, grown on first use (outside graph capture).
+    if ((uint64_t)n * stride > kFusedMaxBytes) {
+        auto &sc = r->scratch[s];
+        if (int rc = grow(r, s, sc.work, work_bytes(n))) return rc;
+        void *work = sc.work.mem.get();
+        hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, n, now_ms, work, s, d_count);
+        if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, n, work, s, true, d_count);
+        if (e != hipSuccess)
+            return hip_fail(e, d_count ? "reassembly launch (device count, split form)" : "reassembly launch (split form)");
+        return E2SAR_HIP_OK;
+    }
+    const hipError_t e = launch_reassemble(r->dev, d_packets, stride, d_lens, n, now_ms, s, d_count);
+    if (e != hipSuccess) return hip_fail(e, d_count ? "reassembly launch (device count)" : "reassembly launch");
+    return E2SAR_HIP_OK;
+}
+
 extern "C" {
 
 int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride,
@@ -717,36 +773,8 @@ int e2sar_hip_reassemble_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint
     if (nPackets == 0) return E2SAR_HIP_OK;
     if (!d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
     if (int st = check_batch(r, d_packets, stride, nPackets)) return st;
-    return reas_launch(r, stream, "reassembly launch", [&](hipStream_t s) -> int {
-        auto &sc = r->scratch[s];
-        if (ref_order(r)) {
-            // classify in arrival order into the internal work buffer, then the scatter kernel
-            if (int rc = ro_prepare(r, s, nPackets)) return rc;
-            if (int rc = grow(r, s, sc.work, work_bytes(nPackets))) return rc;
-            void *work = sc.work.mem.get();
-            hipError_t e = ro_classify(r, s, d_packets, stride, d_lens, nPackets, now_ms, work);
-            if (e == hipSuccess)
-                e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, work, s, cold_loads(r, nPackets, stride));
-            if (e != hipSuccess) return hip_fail(e, "reference-order reassembly launch");
-            return E2SAR_HIP_OK;
-        }
-        // A batch whose datagrams cannot still be in the 256 MiB Infinity Cache (more than
-        // kFusedMaxBytes of slots) is read back from HBM whatever the caller did before, and
-        // there the split form -- classify, then one-round scatter workgroups with streaming
-        // loads -- is the faster one: 8 MiB events at MTU 9000, 70 per launch (65,730
-        // datagrams, BASELINE config 3): 1116 GiB/s fused vs 1302 split.  Internal work buffer
-        // of this stream, grown on first use (outside graph capture).
-        if ((uint64_t)nPackets * stride > kFusedMaxBytes) {
-            if (int rc = grow(r, s, sc.work, work_bytes(nPackets))) return rc;
-            void *work = sc.work.mem.get();
-            hipError_t e = launch_reas_classify(r->dev, d_packets, stride, d_lens, nPackets, now_ms, work, s);
-            if (e == hipSuccess) e = launch_reas_scatter(r->dev, d_packets, stride, nPackets, work, s, true);
-            if (e != hipSuccess) return hip_fail(e, "reassembly launch (split form)");
-            return E2SAR_HIP_OK;
-        }
-        const hipError_t e = launch_reassemble(r->dev, d_packets, stride, d_lens, nPackets, now_ms, s);
-        if (e != hipSuccess) return hip_fail(e, "reassembly launch");
-        return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "reassembly launch", [&](hipStream_t s) {
+        return reassemble(r, s, d_packets, stride, d_lens, nullptr, nPackets, now_ms);
     });
 }
 
@@ -763,23 +791,8 @@ int e2sar_hip_reassemble_batch_dev(e2sar_hip_reas *r, const uint8_t *d_packets, 
         return fail(E2SAR_HIP_ERR_LOGIC, "a REFERENCE_ORDER reassembler takes its datagram count from the host: its key, "
                                          "place and walk launches are sized by it (use e2sar_hip_reassemble_batch)");
     if (maxPackets == 0) return E2SAR_HIP_OK;
-    return reas_launch(r, stream, "reassembly launch (device count)", [&](hipStream_t s) -> int {
-        // Everything the host decides, it decides from the bound: reassemble_batch's choice
-        // of form, cold_loads' of the scatter's loads, the work buffer of this stream.
-        if ((uint64_t)maxPackets * stride > kFusedMaxBytes) {
-            auto &sc = r->scratch[s];
-            if (int rc = grow(r, s, sc.work, work_bytes(maxPackets))) return rc;
-            void *work = sc.work.mem.get();
-            hipError_t e = launch_reas_classify_dev(r->dev, d_packets, stride, d_lens, d_count, maxPackets, now_ms, work, s);
-            if (e == hipSuccess)
-                e = launch_reas_scatter_dev(r->dev, d_packets, stride, d_count, maxPackets, work, s,
-                                            cold_loads(r, maxPackets, stride));
-            if (e != hipSuccess) return hip_fail(e, "reassembly launch (device count, split form)");
-            return E2SAR_HIP_OK;
-        }
-        const hipError_t e = launch_reassemble_dev(r->dev, d_packets, stride, d_lens, d_count, maxPackets, now_ms, s);
-        if (e != hipSuccess) return hip_fail(e, "reassembly launch (device count)");
-        return E2SAR_HIP_OK;
+    return reas_launch(r, stream, "reassembly launch (device count)", [&](hipStream_t s) {
+        return reassemble(r, s, d_packets, stride, d_lens, d_count, maxPackets, now_ms);
     });
 }
 
@@ -894,11 +907,8 @@ int e2sar_hip_reas_collect(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t max
     if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
     if (!d_out || !d_index || !d_counts) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
     if (maxEvents == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxEvents is 0");
-    if (((uintptr_t)d_out & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "output buffer not 256-byte aligned");
-    if (pitch & 15u) return fail(E2SAR_HIP_ERR_PARAMETER, "pitch must be a multiple of 16");
-    if (align == 0) align = 256;
-    if (align < 16 || align > 4096 || (align & (align - 1)))
-        return fail(E2SAR_HIP_ERR_PARAMETER, "align must be 0 or a power of two in [16, 4096]");
+    if (int rc = check_pack_out(d_out)) return rc;
+    if (int rc = check_pack_layout(pitch, align)) return rc;
     // no internal buffer, no memset node: the two launches capture as they are
     return reas_launch(r, stream, "collect launch", [&](hipStream_t s) {
         return launch_collect(r->dev, firstRecord, maxEvents, d_out, outBytes, pitch, align, d_index, d_counts, s);
@@ -923,11 +933,8 @@ int e2sar_hip_reas_build(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t maxRe
         for (uint32_t b = 0; b < a; b++)
             if (dataIds[a] == dataIds[b]) return fail(E2SAR_HIP_ERR_PARAMETER, "a dataId is named twice");
     if (pitch && !nIds) return fail(E2SAR_HIP_ERR_PARAMETER, "cells (pitch > 0) need a dataId list");
-    if (pitch & 15u) return fail(E2SAR_HIP_ERR_PARAMETER, "pitch must be a multiple of 16");
-    if (align == 0) align = 256;
-    if (align < 16 || align > 4096 || (align & (align - 1)))
-        return fail(E2SAR_HIP_ERR_PARAMETER, "align must be 0 or a power of two in [16, 4096]");
-    if (((uintptr_t)d_out & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "output buffer not 256-byte aligned");
+    if (int rc = check_pack_layout(pitch, align)) return rc;
+    if (int rc = check_pack_out(d_out)) return rc;
     if (((uintptr_t)d_work & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
     if (workBytes < build_work_size(maxRecords)) return fail(E2SAR_HIP_ERR_PARAMETER, "build work buffer too small");
     if (outBytes && build_copy_grid(r->dev, maxRecords, nIds, outBytes, pitch, maxGroups) > 0x7FFFFFFFull)

@@ -1,6 +1,6 @@
 // dev_access.hpp -- vector types, shared launch constants, trace macros and memory accessors of the device code, and
 // its wave and workgroup idioms: lane moves and reads, wave scans and min / max, the wave's LDS sync, run heads, and the
-// planners' block scan and first-failure cut.
+// planners' block scan and first-failure cut, and the prefix search of the launches behind them.
 #pragma once
 
 #include "sar_kernels.hpp"
@@ -262,6 +262,42 @@ __device__ __forceinline__ K block_first(bool fails, K key, K *part)
     for (uint32_t w = 0; w < (uint32_t)NW; w++) cut = part[w] < cut ? part[w] : cut;
     return cut;
 }
+
+// The last entry i of [0, n) with prefix(i) <= p, by binary search: prefix is an exclusive
+// prefix sum (non-decreasing, prefix(0) == 0, which is never read) of what the entries hold --
+// copy pieces, seg units -- and p one of the things held; log2(n) reads.  The tie rule: an
+// empty entry shares its prefix with its successor, and the last one wins, so the answer is
+// never an empty entry in front of the one that holds p; trailing empty entries have the
+// total as their prefix, which no p reaches.  n == 0 gives 0 without a read.
+template <typename F>
+__host__ __device__ constexpr uint32_t last_prefix_le(uint32_t p, uint32_t n, F prefix)
+{
+    uint32_t i = 0, hi = n;
+    while (hi - i > 1u) {
+        const uint32_t mid = (i + hi) >> 1;
+        if (prefix(mid) <= p) i = mid;
+        else hi = mid;
+    }
+    return i;
+}
+// entries of 2, 0, 0, 3, 0, 1 and 0 things: p at every boundary, equal prefixes in front
+// (of a table cut to start with them), in the middle and at the end
+namespace prefix_pins {
+constexpr uint32_t kPrefixPin[] = {0, 2, 2, 2, 5, 5, 6};
+constexpr uint32_t prefix_pin(uint32_t p, uint32_t n, uint32_t from = 0)
+{
+    return last_prefix_le(p, n, [from](uint32_t i) { return kPrefixPin[from + i] - kPrefixPin[from]; });
+}
+static_assert(prefix_pin(0, 0) == 0 && prefix_pin(0, 1) == 0 && prefix_pin(9, 1) == 0, "none and one entry");
+static_assert(prefix_pin(0, 2) == 0 && prefix_pin(1, 2) == 0 && prefix_pin(2, 2) == 1, "two entries");
+static_assert(prefix_pin(0, 2, 1) == 1 && prefix_pin(0, 3, 1) == 2 && prefix_pin(0, 4, 1) == 2 && prefix_pin(2, 4, 1) == 2 &&
+                  prefix_pin(3, 4, 1) == 3,
+              "equal prefixes in front: the last of them");
+static_assert(prefix_pin(0, 7) == 0 && prefix_pin(1, 7) == 0 && prefix_pin(2, 7) == 3 && prefix_pin(4, 7) == 3 &&
+                  prefix_pin(5, 7) == 5,
+              "equal prefixes in the middle: the last of them, at every boundary");
+static_assert(prefix_pin(5, 6) == 5 && prefix_pin(4, 5) == 3 && prefix_pin(4, 6) == 3, "the total's last holder");
+}  // namespace prefix_pins
 
 // i / d from d's float reciprocal rd = 1.0f / d and a +-1 correction: exact while the
 // quotient is below 2^22 (the estimate is then off by less than one).  The copy kernels

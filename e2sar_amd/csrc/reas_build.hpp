@@ -110,10 +110,7 @@ __global__ __launch_bounds__(kBuildBlock) void build_plan_kernel(ReasDev R, uint
     BuildSrc *srcOf = reinterpret_cast<BuildSrc *>(work + sizeof(BuildWorkHead));
 
     if (tid == 0) {
-        uint32_t stored = ld_agent(&R.ctl->nCompleted);
-        if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
-        const uint32_t avail = stored > first ? stored - first : 0u;
-        sW = avail < maxRecords ? avail : maxRecords;
+        sW = completed_window(R, first, maxRecords).taken;
         sForeign = 0;
     }
     if (tid < nIds) sIds[tid] = ids.id[tid];
@@ -297,34 +294,6 @@ __global__ __launch_bounds__(kBuildBlock) void build_plan_kernel(ReasDev R, uint
     }
 }
 
-// One 8-KiB piece, starting `base` bytes into an extent of `extent` bytes at dst that holds
-// cp event bytes from src and zeros behind them (zeroTail; a ragged extent ends with the
-// event).  collect_copy_kernel's discipline: every thread issues its kCopyU 16-byte streaming
-// loads before any store; whole 16-byte chunks of the event go as 16-byte stores, its last
-// bytes mod 16 as byte stores; no byte past the event is loaded, none past the extent stored.
-__device__ __forceinline__ void build_copy_piece(const uint8_t *src, uint8_t *dst, uint64_t cp, uint64_t extent,
-                                                 uint64_t base, bool zeroTail)
-{
-    const uint64_t whole = cp & ~15ull, zeroFrom = (cp + 15ull) & ~15ull;
-    u32x4 x[kCopyU];
-#pragma unroll
-    for (int u = 0; u < kCopyU; u++) {
-        const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
-        x[u] = (i + 16 <= whole) ? collect_ld16(src + i) : u32x4{0u, 0u, 0u, 0u};
-    }
-#pragma unroll
-    for (int u = 0; u < kCopyU; u++) {
-        const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
-        if (i + 16 <= whole || (zeroTail && i >= zeroFrom && i < extent)) st16_nt(dst + i, x[u]);
-    }
-    // the chunk the event ends in: its bytes one by one, and in a cell zeros up to the chunk's end
-    if (whole < cp && whole >= base && whole - base < kCopyPiece && threadIdx.x < 16u) {
-        const uint64_t b = whole + threadIdx.x;
-        if (b < cp) st1(dst + b, ld1(src + b));
-        else if (zeroTail) st1(dst + b, (uint8_t)0);
-    }
-}
-
 // One workgroup per 8-KiB piece.  The grid comes from bounds, so a workgroup first reads the
 // piece total build_plan_kernel left in the work buffer on the stream before it, and exits if
 // it is past it.  Cells: the piece's cell by division, its group's record says whether source
@@ -332,10 +301,11 @@ __device__ __forceinline__ void build_copy_piece(const uint8_t *src, uint8_t *ds
 // the group's first member plus the present sources before j; an absent cell is zeros.  The
 // first group record is loaded beside the total, not behind it: the grid's bound keeps its
 // index below maxGroups, so the address is the caller's table whatever the plan took.
-// Ragged: the member by binary search over the piece prefix (the members' `reserved`), as
-// collect_copy_kernel.  The member's bytes lie where its BuildSrc says.  Arena event buffers
-// are 256-byte aligned and every offset at least 16-byte aligned, so there is no unaligned
-// form.  The loop is a guard, not the plan: the grid strides over what the bounds undercount.
+// Ragged: the member by last_prefix_le over the piece prefix (the members' `reserved`), as
+// collect_copy_kernel.  The member's bytes lie where its BuildSrc says, and copy_piece moves
+// them.  Arena event buffers are 256-byte aligned and every offset at least 16-byte aligned,
+// so there is no unaligned form.  The loop is a guard, not the plan: the grid strides over
+// what the bounds undercount.
 __global__ __launch_bounds__(kBlock) void build_copy_kernel(const uint8_t *__restrict__ arena,
                                                             uint8_t *__restrict__ out, uint32_t pitch, uint32_t nIds,
                                                             const e2sar_hip_collect_rec *__restrict__ members,
@@ -360,7 +330,7 @@ __global__ __launch_bounds__(kBlock) void build_copy_kernel(const uint8_t *__res
                 cp = s.bytes < pitch ? s.bytes : pitch;
                 src = arena + s.arenaOffset;
             }
-            build_copy_piece(src, out + (uint64_t)c * pitch, cp, pitch, (uint64_t)(p - c * perCell) * kCopyPiece, true);
+            copy_piece<true>(src, out + (uint64_t)c * pitch, cp, pitch, (uint64_t)(p - c * perCell) * kCopyPiece);
             p += gridDim.x;
             if (p >= total) break;
             c = p / perCell;
@@ -373,15 +343,10 @@ __global__ __launch_bounds__(kBlock) void build_copy_kernel(const uint8_t *__res
     if (p >= total) return;
     const uint32_t n = (uint32_t)counts[1];
     for (; p < total; p += gridDim.x) {
-        uint32_t m = 0, hi = n;                             // the last member whose first piece is <= p
-        while (hi - m > 1u) {
-            const uint32_t mid = (m + hi) >> 1;
-            if (members[mid].reserved <= p) m = mid;
-            else hi = mid;
-        }
+        const uint32_t m = last_prefix_le(p, n, [&](uint32_t i) { return members[i].reserved; });
         const BuildSrc s = srcOf[m];
-        build_copy_piece(arena + s.arenaOffset, out + members[m].outOffset, s.bytes, s.bytes,
-                         (uint64_t)(p - members[m].reserved) * kCopyPiece, false);
+        copy_piece<false>(arena + s.arenaOffset, out + members[m].outOffset, s.bytes, s.bytes,
+                          (uint64_t)(p - members[m].reserved) * kCopyPiece);
     }
 }
 

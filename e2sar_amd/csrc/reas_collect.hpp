@@ -40,12 +40,10 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
     __shared__ uint32_t wavePieces[kWaves], waveCut[kWaves];
     __shared__ uint32_t sAvail, sLimit;
     if (threadIdx.x == 0) {
-        uint32_t stored = ld_agent(&R.ctl->nCompleted);
-        if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
-        const uint32_t avail = stored > first ? stored - first : 0u;
-        uint32_t limit = avail < maxEvents ? avail : maxEvents;
+        const CompletedWindow w = completed_window(R, first, maxEvents);
+        uint32_t limit = w.taken;
         if (pitch && outBytes / pitch < limit) limit = (uint32_t)(outBytes / pitch);
-        sAvail = avail;
+        sAvail = w.avail;
         sLimit = limit;
     }
     __syncthreads();
@@ -115,6 +113,10 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
 // a byte past the event), and in row mode everything from the event's end to the pitch is
 // stored as zeros.  The loop is a guard, not the plan: should the bounds ever undercount the
 // pieces, the grid strides over the rest.
+// The search and the piece are last_prefix_le and copy_piece (build_copy_kernel calls them),
+// kept here in this kernel's own text: on the shared helpers, with the zero tail a run-time
+// flag and as a template argument, a collect case measured outside the parent's bound
+// (DESIGN.md 4.5).
 __global__ __launch_bounds__(kBlock) void collect_copy_kernel(const uint8_t *__restrict__ arena,
                                                               const e2sar_hip_event_rec *__restrict__ completed,
                                                               uint8_t *__restrict__ out, uint32_t pitch,

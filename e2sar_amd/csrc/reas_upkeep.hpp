@@ -32,16 +32,52 @@ __global__ __launch_bounds__(kBlock) void fill_bytes_kernel(uint8_t *p, uint8_t 
     for (uint64_t i = t0; i < body / 16u; i += step) st16(p + head + 16u * i, q);
 }
 
-// Gather copy: blockIdx.y = span; 16-byte loads and stores when both ends are 16-byte
-// aligned (arena event buffers are 256-aligned; callers lay destinations out 64-aligned),
-// bytes otherwise and for the tail.
-// One workgroup copies one 8-KiB piece of one span (blockIdx.y): every thread issues its
-// two 16-byte non-temporal loads before any store, as seg_kernel does, so a large span
-// streams at the plain-copy rate (the bench's HBM calibration copies 1 and 4 GiB with it).
-// 8-KiB pieces copy faster than 16-KiB ones on random bytes (tools/ubench_store.hip:
-// 6.06 vs 5.99 TB/s at 1 GiB, 6.21 vs 5.99 at 4 GiB).
+// One 8-KiB piece of a copy, by one workgroup of kBlock threads: every thread issues its two
+// 16-byte non-temporal loads before any store, as seg_kernel does, so a large copy streams
+// at the plain-copy rate (the bench's HBM calibration copies 1 and 4 GiB with it).  8-KiB
+// pieces copy faster than 16-KiB ones on random bytes (tools/ubench_store.hip: 6.06 vs 5.99
+// TB/s at 1 GiB, 6.21 vs 5.99 at 4 GiB).
 constexpr int kCopyU = 2;
 constexpr uint32_t kCopyPiece = (uint32_t)kBlock * 16u * kCopyU;
+
+// The piece that starts `base` bytes into an extent of `extent` bytes at dst, which holds cp
+// event bytes from src and, with ZERO_TAIL, zeros behind them up to its end (a row or a cell;
+// without, the extent ends with the bytes: a ragged event).  src, dst and a zeroed extent's
+// length are 16-byte aligned.  The discipline of every copy that delivers events: all kCopyU
+// loads of a thread before any store; whole 16-byte chunks of the event go as 16-byte stores,
+// its last bytes mod 16 as byte stores; no byte past the event is loaded, none past the
+// extent stored.  The source is read once: streaming loads (collect's A/B against
+// cache-allocating loads is in DESIGN.md 4.8).  build_copy_kernel's piece; collect_copy_kernel
+// and copy_spans_kernel hold the same body in their own text.
+template <bool ZERO_TAIL>
+__device__ __forceinline__ void copy_piece(const uint8_t *src, uint8_t *dst, uint64_t cp, uint64_t extent, uint64_t base)
+{
+    const uint64_t whole = cp & ~15ull, zeroFrom = (cp + 15ull) & ~15ull;
+    u32x4 x[kCopyU];
+#pragma unroll
+    for (int u = 0; u < kCopyU; u++) {
+        const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
+        x[u] = (i + 16 <= whole) ? ld16_nt(src + i) : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int u = 0; u < kCopyU; u++) {
+        const uint64_t i = base + 16ull * ((uint64_t)u * kBlock + threadIdx.x);
+        if (i + 16 <= whole || (ZERO_TAIL && i >= zeroFrom && i < extent)) st16_nt(dst + i, x[u]);
+    }
+    // the chunk the event ends in: its bytes one by one, and with ZERO_TAIL zeros up to the chunk's end
+    if (whole < cp && whole >= base && whole - base < kCopyPiece && threadIdx.x < 16u) {
+        const uint64_t b = whole + threadIdx.x;
+        if (b < cp) st1(dst + b, ld1(src + b));
+        else if (ZERO_TAIL) st1(dst + b, (uint8_t)0);
+    }
+}
+
+// Gather copy: blockIdx.y = span, blockIdx.x = its 8-KiB piece; 16-byte loads and stores when
+// both ends are 16-byte aligned (arena event buffers are 256-aligned; callers lay
+// destinations out 64-aligned), bytes otherwise and for the tail.  The aligned body is
+// copy_piece's, kept in its own text: the unaligned fallback and the tail loop are this
+// kernel's alone, and with copy_piece as the body (122 instructions for 104) one case of the
+// gather measured outside the parent's bound.
 __global__ __launch_bounds__(kBlock) void copy_spans_kernel(CopySpans cs)
 {
     if (blockIdx.y >= cs.n) return;
@@ -168,6 +204,19 @@ __global__ void reas_compact_finish(ReasDev to)
 // pktBase the exclusive prefix of ceil(bytes / maxPld) (a block-wide scan, 256 records per
 // step), and counts[0] = n, counts[1] = the batch's datagram count.
 
+// The completed-record window of a plan kernel, read by its one thread: the records stored
+// from `first` on, and how many of them a plan bounded by `bound` takes.
+struct CompletedWindow {
+    uint32_t avail, taken;
+};
+__device__ __forceinline__ CompletedWindow completed_window(const ReasDev &R, uint32_t first, uint32_t bound)
+{
+    uint32_t stored = ld_agent(&R.ctl->nCompleted);
+    if (stored > R.queueCapacity) stored = R.queueCapacity;            // records past it were lost
+    const uint32_t avail = stored > first ? stored - first : 0u;
+    return {avail, avail < bound ? avail : bound};
+}
+
 __global__ __launch_bounds__(kBlock) void relay_plan_kernel(ReasDev R, uint32_t first, uint32_t maxEvents,
                                                             uint32_t maxPld, uint64_t lbTick, uint32_t entropyBase,
                                                             e2sar_hip_seg_event *__restrict__ out,
@@ -175,12 +224,7 @@ __global__ __launch_bounds__(kBlock) void relay_plan_kernel(ReasDev R, uint32_t 
 {
     __shared__ uint32_t waveSum[kBlock / 64];
     __shared__ uint32_t sN;
-    if (threadIdx.x == 0) {
-        uint32_t stored = ld_agent(&R.ctl->nCompleted);
-        if (stored > R.queueCapacity) stored = R.queueCapacity;        // records past it were lost
-        const uint32_t avail = stored > first ? stored - first : 0u;
-        sN = avail < maxEvents ? avail : maxEvents;
-    }
+    if (threadIdx.x == 0) sN = completed_window(R, first, maxEvents).taken;
     __syncthreads();
     const uint32_t n = sN;
     uint32_t carry = 0;

@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 namespace e2sar_amd {
 
@@ -403,43 +404,39 @@ static uint32_t reas_group_size(uint32_t n, uint32_t stride, uint32_t fixedG, ui
 // nothing (reas_caps.log).
 constexpr uint32_t kReasJumboPerCU = 2;
 
-hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t stride,
-                             const uint32_t *lens, uint32_t n, uint64_t now, hipStream_t stream)
+// The fused kernels' workgroup size for a slot stride (reas_threads), handed to f as a value
+// whose type carries it; and the dynamic LDS of a launch of that size: the jumbo cap.
+template <typename F>
+static void with_reas_threads(uint32_t stride, F f)
+{
+    reas_threads(stride) == kReasNTSmall ? f(std::integral_constant<int, kReasNTSmall>{})
+                                         : f(std::integral_constant<int, kReasNTJumbo>{});
+}
+template <int NT, typename K>
+static size_t reas_lds(K kernel)
+{
+    if constexpr (NT == kReasNTJumbo) return occupancy_lds(kernel, kReasJumboPerCU);
+    else return 0;
+}
+
+// With d_count the batch is min(*d_count, n) datagrams: the group size, the grid and the
+// kernel's size are those of a batch of n, the only number the host has.
+hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens, uint32_t n,
+                             uint64_t now, hipStream_t stream, const uint32_t *d_count)
 {
     constexpr int U = kReasU;
     if (n == 0) return hipSuccess;
-    const bool small = reas_threads(stride) == kReasNTSmall;
-    const uint32_t G = reas_group_size(n, stride, R.groupSize, small ? reas_resident_groups<U, kReasNTSmall>
-                                                                     : reas_resident_groups<U, kReasNTJumbo>);
-    const uint32_t groups = cdiv(n, G);
-    if (small)
-        hipLaunchKernelGGL((reas_kernel<U, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,
-                           pkts, stride, lens, n, now, G, (const uint32_t *)nullptr);
-    else
-        hipLaunchKernelGGL((reas_kernel<U, kReasNTJumbo>), dim3(groups), dim3(kReasNTJumbo),
-                           occupancy_lds(reas_kernel<U, kReasNTJumbo>, kReasJumboPerCU), stream, R,
-                           pkts, stride, lens, n, now, G, (const uint32_t *)nullptr);
-    return hipGetLastError();
-}
-
-// launch_reassemble for a batch of min(*d_count, maxPackets) datagrams: the group size, the
-// grid and the kernel are those of a batch of maxPackets, the only number the host has.
-hipError_t launch_reassemble_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                 const uint32_t *d_count, uint32_t maxPackets, uint64_t now, hipStream_t stream)
-{
-    constexpr int U = kReasU;
-    if (maxPackets == 0) return hipSuccess;
-    const bool small = reas_threads(stride) == kReasNTSmall;
-    const uint32_t G = reas_group_size(maxPackets, stride, R.groupSize, small ? reas_resident_groups<U, kReasNTSmall>
-                                                                              : reas_resident_groups<U, kReasNTJumbo>);
-    const uint32_t groups = cdiv(maxPackets, G);
-    if (small)
-        hipLaunchKernelGGL((reas_dev_kernel<U, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,
-                           pkts, stride, lens, d_count, maxPackets, now, G);
-    else
-        hipLaunchKernelGGL((reas_dev_kernel<U, kReasNTJumbo>), dim3(groups), dim3(kReasNTJumbo),
-                           occupancy_lds(reas_dev_kernel<U, kReasNTJumbo>, kReasJumboPerCU), stream, R,
-                           pkts, stride, lens, d_count, maxPackets, now, G);
+    with_reas_threads(stride, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        const uint32_t G = reas_group_size(n, stride, R.groupSize, reas_resident_groups<U, NT>);
+        const dim3 groups(cdiv(n, G));
+        if (d_count)
+            hipLaunchKernelGGL((reas_dev_kernel<U, NT>), groups, dim3(NT), reas_lds<NT>(reas_dev_kernel<U, NT>), stream, R,
+                               pkts, stride, lens, d_count, n, now, G);
+        else
+            hipLaunchKernelGGL((reas_kernel<U, NT>), groups, dim3(NT), reas_lds<NT>(reas_kernel<U, NT>), stream, R, pkts,
+                               stride, lens, n, now, G, (const uint32_t *)nullptr);
+    });
     return hipGetLastError();
 }
 
@@ -480,13 +477,19 @@ hipError_t launch_segreas(ChainBatches cb, int lbVersion, uint32_t maxPld, uint3
 
 #endif  // E2SAR_HIP_EXPERIMENTAL
 
+// With d_count (here and in launch_reas_scatter) the batch is min(*d_count, n) datagrams:
+// the grids, the scatter group size and the work view are those of a batch of n.
 hipError_t launch_reas_classify(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                uint32_t n, uint64_t now, void *work, hipStream_t stream)
+                                uint32_t n, uint64_t now, void *work, hipStream_t stream, const uint32_t *d_count)
 {
     if (n == 0) return hipSuccess;
     const WorkView w = work_view(work, n);
-    hipLaunchKernelGGL(reas_classify_kernel, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, R, pkts, stride, lens,
-                       n, now, w.info, w.fin);
+    const dim3 grid(cdiv(n, kBlock));
+    if (d_count)
+        hipLaunchKernelGGL(reas_classify_dev_kernel, grid, dim3(kBlock), 0, stream, R, pkts, stride, lens, d_count, n, now,
+                           w.info, w.fin);
+    else
+        hipLaunchKernelGGL(reas_classify_kernel, grid, dim3(kBlock), 0, stream, R, pkts, stride, lens, n, now, w.info, w.fin);
     return hipGetLastError();
 }
 
@@ -532,7 +535,7 @@ static void with_scatter_variant(uint32_t stride, bool nt, F f)
 }
 
 hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t stride, uint32_t n,
-                               const void *work, hipStream_t stream, bool nt)
+                               const void *work, hipStream_t stream, bool nt, const uint32_t *d_count)
 {
     if (n == 0) return hipSuccess;
     const WorkView w = work_view(work, n);
@@ -540,38 +543,12 @@ hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t s
     const uint32_t G = scatter_geometry(stride, n, blocks);
     with_scatter_variant(stride, nt, [&](auto v) {
         using V = decltype(v);
-        const auto kernel = reas_scatter_kernel<V::U, V::NT, V::STAGE, V::TB>;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
-                           n, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
-    });
-    return hipGetLastError();
-}
-
-// The split form for a batch of min(*d_count, maxPackets) datagrams: grids, the scatter
-// group size and the work view are those of a batch of maxPackets.
-hipError_t launch_reas_classify_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                    const uint32_t *d_count, uint32_t maxPackets, uint64_t now, void *work,
-                                    hipStream_t stream)
-{
-    if (maxPackets == 0) return hipSuccess;
-    const WorkView w = work_view(work, maxPackets);
-    hipLaunchKernelGGL(reas_classify_dev_kernel, dim3(cdiv(maxPackets, kBlock)), dim3(kBlock), 0, stream, R, pkts, stride,
-                       lens, d_count, maxPackets, now, w.info, w.fin);
-    return hipGetLastError();
-}
-
-hipError_t launch_reas_scatter_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *d_count,
-                                   uint32_t maxPackets, const void *work, hipStream_t stream, bool nt)
-{
-    if (maxPackets == 0) return hipSuccess;
-    const WorkView w = work_view(work, maxPackets);
-    uint32_t blocks = 0;
-    const uint32_t G = scatter_geometry(stride, maxPackets, blocks);
-    with_scatter_variant(stride, nt, [&](auto v) {
-        using V = decltype(v);
-        const auto kernel = reas_scatter_dev_kernel<V::U, V::NT, V::STAGE, V::TB>;
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
-                           d_count, maxPackets, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
+        const auto launch = [&](auto kernel, auto... count) {
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(V::TB), scatter_lds(kernel, V::STAGE, V::NT), stream, R, pkts, stride,
+                               count..., n, G, (const PktInfo *)w.info, (const FinishRec *)w.fin);
+        };
+        if (d_count) launch(reas_scatter_dev_kernel<V::U, V::NT, V::STAGE, V::TB>, d_count);
+        else launch(reas_scatter_kernel<V::U, V::NT, V::STAGE, V::TB>);
     });
     return hipGetLastError();
 }

@@ -268,12 +268,12 @@ hipError_t launch_build(const ReasDev &R, uint32_t first, uint32_t maxRecords, c
                         uint8_t *out, uint64_t outBytes, uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_members,
                         e2sar_hip_built_rec *d_groups, uint32_t maxGroups, uint64_t *d_counts, void *d_work,
                         hipStream_t stream);
-hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t stride,
-                             const uint32_t *lens, uint32_t n, uint64_t now, hipStream_t stream);
-// The same for min(*d_count, maxPackets) datagrams, d_count a device word the kernel reads:
-// one launch whose geometry is that of a batch of maxPackets (e2sar_hip_reassemble_batch_dev)
-hipError_t launch_reassemble_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                 const uint32_t *d_count, uint32_t maxPackets, uint64_t now, hipStream_t stream);
+// d_count (optional, here and in the classify and scatter launches): the batch is
+// min(*d_count, n) datagrams, d_count a device word the kernels read; the launch's geometry
+// -- and the layout of `work`, which holds work_bytes(n) -- is that of a batch of n
+// (e2sar_hip_reassemble_batch_dev)
+hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens, uint32_t n,
+                             uint64_t now, hipStream_t stream, const uint32_t *d_count = nullptr);
 // XCD-matched groups of a planned batch (seg_kernel's stripes) and the fused reassembly over them
 uint32_t seg_groups(const e2sar_hip_seg_event *ev, uint32_t nEvents, uint32_t maxPacketsPerEvent, uint32_t maxPld,
                     uint32_t stride, uint32_t *starts, uint32_t cap);
@@ -300,15 +300,9 @@ struct ChainBatches {
 hipError_t launch_segreas(ChainBatches cb, int lbVersion, uint32_t maxPld, uint32_t stride, const ReasDev &R,
                           uint64_t now, hipStream_t stream);
 hipError_t launch_reas_classify(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                uint32_t n, uint64_t now, void *work, hipStream_t stream);
-hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t stride, uint32_t n,
-                               const void *work, hipStream_t stream, bool nt);   // nt: streaming datagram loads
-// and the split form for them: `work` holds work_bytes(maxPackets) and is laid out for maxPackets
-hipError_t launch_reas_classify_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
-                                    const uint32_t *d_count, uint32_t maxPackets, uint64_t now, void *work,
-                                    hipStream_t stream);
-hipError_t launch_reas_scatter_dev(const ReasDev &R, const uint8_t *pkts, uint32_t stride, const uint32_t *d_count,
-                                   uint32_t maxPackets, const void *work, hipStream_t stream, bool nt);
+                                uint32_t n, uint64_t now, void *work, hipStream_t stream, const uint32_t *d_count = nullptr);
+hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t stride, uint32_t n, const void *work,
+                               hipStream_t stream, bool nt, const uint32_t *d_count = nullptr);   // nt: streaming datagram loads
 hipError_t launch_reas_scatter_classify(const ReasDev &R, uint32_t stride, const uint8_t *spk, uint32_t sn,
                                         const void *swork, const uint8_t *cpk, const uint32_t *clens, uint32_t cn,
                                         uint64_t now, void *cwork, hipStream_t stream, bool nt);

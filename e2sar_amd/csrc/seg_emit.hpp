@@ -108,12 +108,10 @@ __global__ __launch_bounds__(kBlock) void emit_plan_kernel(EmitSrc S, EmitNum N,
 // range, as seg_kernel's, but numbered flat over the taken events, so an event wastes less
 // than one unit whatever the bound on its length was.  The grid comes from bounds, so a
 // workgroup first reads what emit_plan_kernel wrote on the stream before it: the unit total;
-// a workgroup past it exits.  The others find their event -- the LAST event whose first
-// unit is <= the workgroup's index: a binary search, log2(n) workgroup-uniform loads of a
-// table that sits in L2.  An empty event shares its first unit with its successor, so the
-// last such event is never an empty one in front of it; and a trailing empty event's first
-// unit is the total, which no running workgroup reaches.  No XCD stripes: matching them to
-// a reassembler needs a group table only the host can build (seg_groups).
+// a workgroup past it exits.  The others find their event by last_prefix_le over the first
+// units, workgroup-uniform loads of a table that sits in L2; its tie rule keeps an empty
+// event from taking its successor's units.  No XCD stripes: matching them to a reassembler
+// needs a group table only the host can build (seg_groups).
 template <int U>
 __global__ __launch_bounds__(kSegBlock) void seg_flat_kernel(const e2sar_hip_seg_event *__restrict__ events,
                                                              const uint32_t *__restrict__ counts, int lbVersion,
@@ -125,12 +123,7 @@ __global__ __launch_bounds__(kSegBlock) void seg_flat_kernel(const e2sar_hip_seg
     // workgroup works, and those all sit on four of the eight XCDs
     const uint32_t p = blockIdx.x;
     if (p >= counts[4]) return;                             // no unit: also when no event was taken
-    uint32_t e = 0, hi = counts[0];
-    while (hi - e > 1u) {
-        const uint32_t mid = (e + hi) >> 1;
-        if (events[mid].reserved <= p) e = mid;
-        else hi = mid;
-    }
+    const uint32_t e = last_prefix_le(p, counts[0], [&](uint32_t i) { return events[i].reserved; });
     seg_unit<U, false, kSegBlock>(events, e, p - events[e].reserved, lbVersion, maxPld, pkts, stride, lens, 1u, nullptr);
 }
 

@@ -24,8 +24,10 @@ KERNELS = {
     "reas_recycle_kernel": 1, "reas_compact_kernel": 1, "reas_compact_finish": 1, "relay_plan_kernel": 1,
     "route_hist_kernel": 1, "route_scan_kernel": 1, "route_pack_kernel": 1, "route_append_kernel": 1,
     "collect_plan_kernel": 1, "collect_copy_kernel": 1, "emit_plan_kernel": 1, "seg_flat_kernel": 2,
+    "build_plan_kernel": 1, "build_copy_kernel": 1,
+    "reas_dev_kernel": 2, "reas_classify_dev_kernel": 1, "reas_scatter_dev_kernel": 6,
 }
-assert sum(KERNELS.values()) == 38
+assert sum(KERNELS.values()) == 49
 
 
 def _remarks(src, tmp_path):

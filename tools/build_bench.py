@@ -23,34 +23,24 @@ one-workgroup plans grow with the window.
                               [--mtu 1500] [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).
 """
-import argparse
 import ctypes as C
-import json
 import os
-import statistics
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_method
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = ab_method.parser(events=None)          # the events are event numbers x sources here
     ap.add_argument("--event-nums", type=int, default=41)
     ap.add_argument("--sources", type=int, default=5)
-    ap.add_argument("--event-bytes", type=int, default=1 << 20)
-    ap.add_argument("--mtu", type=int, default=1500)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
     import torch
     from e2sar_amd import sar, _capi
 
-    if not torch.cuda.is_available():
-        sys.exit("build_bench needs a GPU: nothing is measured without one")
+    ab_method.need_gpu("build_bench")
     dev = torch.device("cuda:0")
     ctx = sar.Context(0)
     seg = sar.DeviceSegmenter(ctx, mtu=args.mtu, lb_hdr_version=2)
@@ -81,26 +71,8 @@ def main():
         torch.cuda.synchronize()
         return R, src, n_ev
 
-    spin = 300_000                              # clocks; covers the host side of a call
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(spin)                 # the host enqueues the timed call while the device spins
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3          # us
-
     def measure(forms):
-        us = {name: [] for name in forms}
-        for rep in range(args.warmup + args.reps):
-            for name, fn in forms.items():
-                t_us = timed(fn)
-                if rep >= args.warmup:
-                    us[name].append(t_us)
-        return {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2),
-                       "p90_us": round(sorted(v)[int(0.9 * (len(v) - 1))], 2)} for name, v in us.items()}
+        return ab_method.summary(ab_method.measure(forms, args))
 
     def calls(R, out, n_max, ids, pitch):
         """The collect and build calls over R's records as closures of (out_bytes) -> callable."""
@@ -190,12 +162,7 @@ def main():
         })
     R.close()
 
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    ab_method.write_line(result, args.out)
 
 
 if __name__ == "__main__":

@@ -19,33 +19,21 @@ form's output is compared with the events' source bytes once.
                                 [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).  Rates count read + write bytes.
 """
-import argparse
 import ctypes as C
-import json
 import os
-import statistics
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_method
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--events", type=int, default=205)
-    ap.add_argument("--event-bytes", type=int, default=1 << 20)
-    ap.add_argument("--mtu", type=int, default=1500)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ab_method.parser().parse_args()
 
     import torch
     from e2sar_amd import sar, _capi
 
-    if not torch.cuda.is_available():
-        sys.exit("collect_bench needs a GPU: nothing is measured without one")
+    ab_method.need_gpu("collect_bench")
     dev = torch.device("cuda:0")
     ctx = sar.Context(0)
     E, B = args.events, args.event_bytes
@@ -86,62 +74,40 @@ def main():
             arr[k] = _capi.CopySpan(int(r["data"]), out.data_ptr() + k * ev_stride, int(r["bytes"]))
         return arr, t
 
+    sp, t = None, None                          # the span table of the batch in the arena, and its records
+
+    def fresh():
+        nonlocal sp, t
+        reassemble()
+        sp, t = spans()
+
     forms = {
-        "ragged": lambda sp: R.collect(out, index, counts, 0, E, 0, 256),
-        "rows": lambda sp: R.collect(out, index, counts, 0, E, pitch),
-        "spans": lambda sp: _capi.check(_capi.lib().e2sar_hip_copy_spans(
+        "ragged": lambda: R.collect(out, index, counts, 0, E, 0, 256),
+        "rows": lambda: R.collect(out, index, counts, 0, E, pitch),
+        "spans": lambda: _capi.check(_capi.lib().e2sar_hip_copy_spans(
             ctx.handle, sp, len(sp), C.c_void_p(int(torch.cuda.current_stream().cuda_stream)))),
     }
 
     # every form delivers every event's bytes
-    reassemble()
-    sp, t = spans()
+    fresh()
     assert len(sp) == E, len(sp)
     host = src[:, :B].cpu().numpy()
     for name, fn in forms.items():
         out.zero_()
-        fn(sp)
+        fn()
         torch.cuda.synchronize()
         step = pitch if name == "rows" else ev_stride
         got = out[: E * step].view(E, step)[:, :B].cpu().numpy()
         for k, r in enumerate(t):
             assert np.array_equal(got[k], host[int(r["eventNum"])]), (name, k)
 
-    spin = 300_000                              # clocks; covers the host side of a call
-
-    def timed(fn, sp):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(spin)                 # the host enqueues the timed calls while the device spins
-        a.record()
-        fn(sp)
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3          # us
-
     result = {"tool": "collect_bench", "events": E, "event_bytes": B, "mtu": args.mtu, "reps": args.reps,
               "lib": os.path.basename(_capi.LIB_PATH), "device": torch.cuda.get_device_name(0), "states": {}}
-    moved = 2 * E * B
+    moved = {name: 2 * E * B for name in forms}
     for state in ("steady", "fresh"):
-        us = {name: [] for name in forms}
-        for rep in range(args.warmup + args.reps):
-            for name, fn in forms.items():
-                if state == "fresh":
-                    reassemble()
-                    sp, _ = spans()
-                t_us = timed(fn, sp)
-                if rep >= args.warmup:
-                    us[name].append(t_us)
-        result["states"][state] = {
-            name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2),
-                   "p90_us": round(sorted(v)[int(0.9 * (len(v) - 1))], 2),
-                   "TBps_median": round(moved / statistics.median(v) / 1e6, 3)}
-            for name, v in us.items()}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+        us = ab_method.measure(forms, args, prepare=fresh if state == "fresh" else None)
+        result["states"][state] = ab_method.summary(us, moved)
+    ab_method.write_line(result, args.out)
     R.close()
 
 

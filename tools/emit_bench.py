@@ -26,63 +26,33 @@ Every form's datagrams are compared with `batch`'s (headline) or `dev`'s (skewed
                              [--skew-max B] [--mtu 1500] [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).  Rates count event bytes read + datagram bytes written.
 """
-import argparse
-import json
 import os
-import statistics
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_method
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--events", type=int, default=205)
-    ap.add_argument("--event-bytes", type=int, default=1 << 20)
+    ap = ab_method.parser()
     ap.add_argument("--skew-rows", type=int, default=1024)
     ap.add_argument("--skew-min", type=int, default=4096)
     ap.add_argument("--skew-max", type=int, default=None)
-    ap.add_argument("--mtu", type=int, default=1500)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
     import torch
     from e2sar_amd import sar, _capi
 
-    if not torch.cuda.is_available():
-        sys.exit("emit_bench needs a GPU: nothing is measured without one")
+    ab_method.need_gpu("emit_bench")
     dev = torch.device("cuda:0")
     ctx = sar.Context(0)
     B = args.event_bytes
     seg = sar.DeviceSegmenter(ctx, mtu=args.mtu, lb_hdr_version=2)
     per_row = sar.num_packets(B, seg.max_pld)
     numbering = dict(event_num_base=1000, lb_tick_base=1 << 48, lb_tick_step=1, data_id=4321, entropy_base=1)
-    spin = 300_000                              # clocks; covers the host side of a call
-
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(spin)                 # the host enqueues the timed calls while the device spins
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3          # us
 
     def measure(forms, moved):
-        us = {name: [] for name in forms}
-        for rep in range(args.warmup + args.reps):
-            for name, fn in forms.items():
-                t_us = timed(fn)
-                if rep >= args.warmup:
-                    us[name].append(t_us)
-        return {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2),
-                       "p90_us": round(sorted(v)[int(0.9 * (len(v) - 1))], 2),
-                       "TBps_median": round(moved.get(name, 0) / statistics.median(v) / 1e6, 3)}
-                for name, v in us.items()}
+        return ab_method.summary(ab_method.measure(forms, args), moved)
 
     def batch(rows_n, lengths):
         """-> the buffers of one batch of rows_n rows with the given host lengths."""
@@ -158,12 +128,7 @@ def main():
                        "units_of_work": int(sum(-(-sar.num_packets(int(x), seg.max_pld) * spc // unit) for x in lengths))},
         "forms": measure(forms, moved)}
 
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    ab_method.write_line(result, args.out)
 
 
 if __name__ == "__main__":

@@ -25,40 +25,24 @@ dev_full's events are compared with the source rows once.
   python tools/reas_dev_bench.py [--events 205] [--event-bytes 1048576] [--mtu 1500] [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).  Rates count datagram bytes read + event bytes written.
 """
-import argparse
-import json
 import os
-import statistics
-import sys
 
-import numpy as np
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ab_method
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--events", type=int, default=205)
-    ap.add_argument("--event-bytes", type=int, default=1 << 20)
-    ap.add_argument("--mtu", type=int, default=1500)
-    ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ab_method.parser().parse_args()
 
     import torch
     from e2sar_amd import sar, _capi
 
-    if not torch.cuda.is_available():
-        sys.exit("reas_dev_bench needs a GPU: nothing is measured without one")
+    ab_method.need_gpu("reas_dev_bench")
     dev = torch.device("cuda:0")
     ctx = sar.Context(0)
     E, B = args.events, args.event_bytes
     seg = sar.DeviceSegmenter(ctx, mtu=args.mtu, lb_hdr_version=2)
     per_row = sar.num_packets(B, seg.max_pld)
     numbering = dict(event_num_base=1000, lb_tick_base=1 << 48, lb_tick_step=1, data_id=4321, entropy_base=1)
-    spin = 300_000                              # clocks; covers the host side of a call
-
     g = torch.Generator(device=dev)
     g.manual_seed(1234 + E)
     rows = torch.randint(0, 256, (E, B), dtype=torch.uint8, device=dev, generator=g)
@@ -128,17 +112,7 @@ def main():
     graph.replay()
     delivered("chain_graph", E)
 
-    def timed(fn, before=None):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(spin)                 # the host enqueues the timed calls while the device spins
-        if before:
-            before()
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        return a.elapsed_time(b) * 1e3          # us
-
+    # (fn, before): `before` is the untimed segmentation, enqueued inside the spin
     forms = {
         "host": (lambda: R.reassemble(pk, seg.stride, ln, n), fresh),
         "dev_full": (lambda: R.reassemble_dev(pk, seg.stride, ln, d_n[0:1], max_packets=n), fresh),
@@ -151,25 +125,11 @@ def main():
     tail = B - (per_row - 1) * seg.max_pld
     full_bytes = E * ((per_row - 1) * dgram + 36 + tail) + E * B
     moved = {"host": full_bytes, "dev_full": full_bytes}
-    us = {name: [] for name in forms}
-    for rep in range(args.warmup + args.reps):
-        for name, (fn, before) in forms.items():
-            t_us = timed(fn, before)
-            if rep >= args.warmup:
-                us[name].append(t_us)
+    us = ab_method.measure(forms, args)
     result = {"tool": "reas_dev_bench", "events": E, "event_bytes": B, "mtu": args.mtu, "reps": args.reps,
               "datagrams": n, "sparse_datagrams": sparse, "lib": os.path.basename(_capi.LIB_PATH),
-              "device": torch.cuda.get_device_name(0),
-              "forms": {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2),
-                               "p90_us": round(sorted(v)[int(0.9 * (len(v) - 1))], 2),
-                               "TBps_median": round(moved.get(name, 0) / statistics.median(v) / 1e6, 3)}
-                        for name, v in us.items()}}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+              "device": torch.cuda.get_device_name(0), "forms": ab_method.summary(us, moved)}
+    ab_method.write_line(result, args.out)
 
 
 if __name__ == "__main__":
