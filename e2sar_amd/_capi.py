@@ -133,6 +133,23 @@ class CollectRec(C.Structure):
 COLLECT_TRUNCATED = 1         # CollectRec.flags, row mode: the event is longer than the pitch
 
 
+class TurnMarks(C.Structure):
+    """e2sar_hip_turn_marks: when e2sar_hip_reas_turn runs, and how long it carries an event."""
+    _fields_ = [
+        ("arenaMark", C.c_uint64),
+        ("recordMark", C.c_uint32),
+        ("tableMark", C.c_uint32),
+        ("maxCarries", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+TURN_SKIPPED = 0              # d_status[0] of e2sar_hip_reas_turn: no mark reached
+TURN_RAN = 1
+TURN_UNCONSUMED = 2           # skipped: a completed record has not been collected
+TURN_NEVER_LOST = 0xFFFFFFFF  # TurnMarks.maxCarries: carry every event in progress, however often
+
+
 class BuiltRec(C.Structure):
     """e2sar_hip_built_rec: one built event of e2sar_hip_reas_build, members [firstMember, +nMembers)."""
     _fields_ = [
@@ -185,6 +202,7 @@ assert C.sizeof(EventRec) == 32
 assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
 assert C.sizeof(BuiltRec) == 32
+assert C.sizeof(TurnMarks) == 24
 
 vp = C.c_void_p
 i = C.c_int
@@ -231,6 +249,8 @@ SIGNATURES = {
     "e2sar_hip_seg_emit": (i, [vp, C.POINTER(SegSource), C.POINTER(SegNumbering), u32, i, u32, vp, u32, u32, vp, vp, vp, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),
     "e2sar_hip_reas_collect": (i, [vp, u32, u32, vp, u64, u32, u32, vp, vp, vp]),
+    "e2sar_hip_reas_collect_next": (i, [vp, vp, u32, vp, u64, u32, u32, vp, vp, vp]),
+    "e2sar_hip_reas_turn": (i, [vp, vp, C.POINTER(TurnMarks), vp, vp]),
     "e2sar_hip_reas_build_work_bytes": (sz, [u32]),
     "e2sar_hip_reas_build": (i, [vp, u32, u32, C.POINTER(C.c_uint16), u32, vp, u64, u32, u32, vp, vp, u32, vp, vp, sz, vp]),
     "e2sar_hip_reas_create": (i, [vp, C.POINTER(ReasConfig), C.POINTER(vp)]),

@@ -111,8 +111,8 @@ struct GrowBuf {
 
 // The order in which a reassembler's memory goes is the reverse of the declarations below:
 // the destructor waits for the device, then the event, the retired buffers, the per-stream
-// scratch, both arenas, the alternate table and the state block are released, and the
-// reference on the context last.
+// scratch, both arenas, the turn's move list, the alternate table and the state block are
+// released, and the reference on the context last.
 struct e2sar_hip_reas {
     CtxRef ctx;                      // first, so destroyed last: the destructor sets its device
     e2sar_hip_reas_config cfg{};
@@ -121,6 +121,7 @@ struct e2sar_hip_reas {
     ReasDev alt{};                   // second slots + arena (COMPACTABLE), same ctl/lists
     DevMem state;                    // slots | ctl | shards | occupancy shards | completed | lost
     DevMem altSlots;
+    DevMem turnMoves;                // the turn's move list (COMPACTABLE): kTurnMoveBytes per table slot
     DevMem arena[2];                 // owned by identity, whichever of dev / alt points at which
     // Internal buffers, one set PER STREAM (two batches launched on different streams must
     // not share work records or ready counters while both run): the reference-order sort
@@ -682,6 +683,7 @@ int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, 
     if (cfg->flags & E2SAR_HIP_REAS_COMPACTABLE) {
         e = dev_alloc(r->altSlots, slotsB);
         if (e == hipSuccess) e = dev_alloc(r->arena[1], arenaB);
+        if (e == hipSuccess) e = dev_alloc(r->turnMoves, kTurnMoveBytes * (size_t)T);
         if (e != hipSuccess) return alloc_fail(e, "hipMalloc(alternate arena)");
         r->alt.slots = static_cast<ReasSlot *>(r->altSlots.get());
         r->alt.arena = static_cast<uint8_t *>(r->arena[1].get());
@@ -912,6 +914,39 @@ int e2sar_hip_reas_collect(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t max
     // no internal buffer, no memset node: the two launches capture as they are
     return reas_launch(r, stream, "collect launch", [&](hipStream_t s) {
         return launch_collect(r->dev, firstRecord, maxEvents, d_out, outBytes, pitch, align, d_index, d_counts, s);
+    });
+}
+
+int e2sar_hip_reas_collect_next(e2sar_hip_reas *r, uint32_t *d_cursor, uint32_t maxEvents, uint8_t *d_out,
+                                uint64_t outBytes, uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index,
+                                uint64_t *d_counts, void *stream)
+{
+    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
+    if (!d_cursor) return fail(E2SAR_HIP_ERR_PARAMETER, "cursor is NULL");
+    if (!d_out || !d_index || !d_counts) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (maxEvents == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "maxEvents is 0");
+    if (int rc = check_pack_out(d_out)) return rc;
+    if (int rc = check_pack_layout(pitch, align)) return rc;
+    // collect's two launches, with the cursor where firstRecord stood
+    return reas_launch(r, stream, "collect_next launch", [&](hipStream_t s) {
+        return launch_collect(r->dev, 0u, maxEvents, d_out, outBytes, pitch, align, d_index, d_counts, s, d_cursor);
+    });
+}
+
+int e2sar_hip_reas_turn(e2sar_hip_reas *r, uint32_t *d_cursor, const e2sar_hip_turn_marks *marks, uint64_t *d_status,
+                        void *stream)
+{
+    if (!r) return fail(E2SAR_HIP_ERR_PARAMETER, "reas is NULL");
+    if (!d_cursor || !marks || !d_status) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL argument");
+    if (marks->reserved != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "marks.reserved must be 0");
+    // (both set at creation and never changed, so no lock to ask)
+    if (!r->alt.slots) return fail(E2SAR_HIP_ERR_LOGIC, "reassembler was not created COMPACTABLE");
+    if (ref_order(r))
+        return fail(E2SAR_HIP_ERR_LOGIC, "turn is not available in reference-order mode (a slot's carry count would "
+                                         "age the key's next item)");
+    // no buffer that grows, no memset node, no wait: the four launches capture as they are
+    return reas_launch(r, stream, "turn launch", [&](hipStream_t s) {
+        return launch_turn(r->dev, r->alt, d_cursor, *marks, d_status, r->turnMoves.get(), s);
     });
 }
 

@@ -30,24 +30,33 @@ __device__ __forceinline__ u32x4 collect_ld16(const uint8_t *p) { return ld16_nt
 // taken, even if it would fit (record order is kept); a second scan, over the taken records
 // only, gives each its first copy piece -- the exclusive prefix of ceil(extent / 8 KiB),
 // kept in the index record's `reserved` word, where collect_copy_kernel searches it.
-__global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_t first, uint32_t maxEvents,
-                                                              uint64_t outBytes, uint32_t pitch, uint32_t align,
-                                                              e2sar_hip_collect_rec *__restrict__ index,
-                                                              uint64_t *__restrict__ counts)
+//
+// The plan is one body under two kernels.  collect_plan_kernel takes `first` from the host.
+// collect_next_plan_kernel (CURSOR) reads it from a device word when it runs, takes nothing
+// when outBytes is 0, and leaves the word grown by the n it took: the cursor of a consumer
+// that never asks the host where it stands (e2sar_hip_reas_collect_next).
+template <bool CURSOR>
+__device__ __forceinline__ void collect_plan(const ReasDev &R, uint32_t first, uint32_t *cursor, uint32_t maxEvents,
+                                             uint64_t outBytes, uint32_t pitch, uint32_t align,
+                                             e2sar_hip_collect_rec *__restrict__ index, uint64_t *__restrict__ counts)
 {
     constexpr int kWaves = kBlock / 64;
     __shared__ uint64_t wavePad[kWaves], waveTaken[kWaves], waveCopied[kWaves];
     __shared__ uint32_t wavePieces[kWaves], waveCut[kWaves];
-    __shared__ uint32_t sAvail, sLimit;
+    __shared__ uint32_t sAvail, sLimit, sFirst;
     if (threadIdx.x == 0) {
+        if (CURSOR) first = *cursor;
         const CompletedWindow w = completed_window(R, first, maxEvents);
         uint32_t limit = w.taken;
         if (pitch && outBytes / pitch < limit) limit = (uint32_t)(outBytes / pitch);
+        if (CURSOR && outBytes == 0) limit = 0;
         sAvail = w.avail;
         sLimit = limit;
+        if (CURSOR) sFirst = first;
     }
     __syncthreads();
     const uint32_t limit = sLimit;
+    if (CURSOR) first = sFirst;
     uint32_t n = limit, pieces = 0;
     uint64_t carry = 0, copied = 0;                        // bytes of `out` spanned, event bytes copied
     for (uint32_t b0 = 0; b0 < limit; b0 += kBlock) {
@@ -98,7 +107,24 @@ __global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_
         counts[1] = carry;
         counts[2] = sAvail - n;
         counts[3] = copied;
+        if (CURSOR) *cursor = first + n;
     }
+}
+
+__global__ __launch_bounds__(kBlock) void collect_plan_kernel(ReasDev R, uint32_t first, uint32_t maxEvents,
+                                                              uint64_t outBytes, uint32_t pitch, uint32_t align,
+                                                              e2sar_hip_collect_rec *__restrict__ index,
+                                                              uint64_t *__restrict__ counts)
+{
+    collect_plan<false>(R, first, nullptr, maxEvents, outBytes, pitch, align, index, counts);
+}
+
+__global__ __launch_bounds__(kBlock) void collect_next_plan_kernel(ReasDev R, uint32_t *__restrict__ cursor,
+                                                                   uint32_t maxEvents, uint64_t outBytes, uint32_t pitch,
+                                                                   uint32_t align, e2sar_hip_collect_rec *__restrict__ index,
+                                                                   uint64_t *__restrict__ counts)
+{
+    collect_plan<true>(R, 0u, cursor, maxEvents, outBytes, pitch, align, index, counts);
 }
 
 // One workgroup per 8-KiB piece of one event's extent (its bytes, or its row of `pitch`).
@@ -164,6 +190,33 @@ __global__ __launch_bounds__(kBlock) void collect_copy_kernel(const uint8_t *__r
             if (b < cp) st1(dst + b, ld1(src + b));
             else if (pitch) st1(dst + b, (uint8_t)0);
         }
+    }
+}
+
+// collect_copy_kernel for e2sar_hip_reas_collect_next: the first taken record is not the
+// host's to name -- it is the cursor collect_next_plan_kernel left, minus the n it took, from
+// the list's base.  The same pieces, found and moved by the shared helpers; collect_copy_kernel
+// keeps its own text, instruction for instruction, and so what it measured.
+__global__ __launch_bounds__(kBlock) void collect_next_copy_kernel(const uint8_t *__restrict__ arena,
+                                                                   const e2sar_hip_event_rec *__restrict__ completed,
+                                                                   const uint32_t *__restrict__ cursor,
+                                                                   uint8_t *__restrict__ out, uint32_t pitch,
+                                                                   const e2sar_hip_collect_rec *__restrict__ index,
+                                                                   const uint64_t *__restrict__ counts)
+{
+    const uint32_t n = (uint32_t)counts[0];
+    if (n == 0) return;
+    completed += *cursor - n;
+    const uint32_t perRow = collect_pieces(pitch);
+    const uint32_t total = index[n - 1u].reserved + (pitch ? perRow : collect_pieces(index[n - 1u].bytes));
+    for (uint32_t p = blockIdx.x; p < total; p += gridDim.x) {
+        const uint32_t ev = pitch ? p / perRow : last_prefix_le(p, n, [&](uint32_t i) { return index[i].reserved; });
+        const uint32_t bytes = index[ev].bytes;
+        const uint8_t *src = arena + completed[ev].arenaOffset;
+        uint8_t *dst = out + index[ev].outOffset;
+        const uint64_t base = (uint64_t)(p - index[ev].reserved) * kCopyPiece;
+        if (pitch) copy_piece<true>(src, dst, bytes < pitch ? bytes : pitch, pitch, base);
+        else copy_piece<false>(src, dst, bytes, bytes, base);
     }
 }
 

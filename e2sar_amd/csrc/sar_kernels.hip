@@ -18,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_order, reas_upkeep, reas_collect, reas_build, seg_emit, route), all
+// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -35,6 +35,7 @@
 #include "reas_devcount.hpp"
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
+#include "reas_turn.hpp"
 #include "reas_collect.hpp"
 #include "reas_build.hpp"
 #include "seg_emit.hpp"
@@ -257,10 +258,14 @@ hipError_t launch_relay_plan(const ReasDev &R, uint32_t first, uint32_t maxEvent
 
 hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint8_t *out, uint64_t outBytes,
                           uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index, uint64_t *d_counts,
-                          hipStream_t stream)
+                          hipStream_t stream, uint32_t *d_cursor)
 {
-    hipLaunchKernelGGL(collect_plan_kernel, dim3(1), dim3(kBlock), 0, stream, R, first, maxEvents, outBytes, pitch, align,
-                       d_index, d_counts);
+    if (d_cursor)
+        hipLaunchKernelGGL(collect_next_plan_kernel, dim3(1), dim3(kBlock), 0, stream, R, d_cursor, maxEvents, outBytes,
+                           pitch, align, d_index, d_counts);
+    else
+        hipLaunchKernelGGL(collect_plan_kernel, dim3(1), dim3(kBlock), 0, stream, R, first, maxEvents, outBytes, pitch,
+                           align, d_index, d_counts);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || outBytes == 0) return e;                  // no room: the plan wrote n = 0
     // The copy's grid, from bounds only: n events of B bytes in all are at most B / piece + n
@@ -269,8 +274,14 @@ hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, 
     const uint32_t most = std::min(maxEvents, R.queueCapacity);
     const uint64_t bound = pitch ? (uint64_t)most * pitch : R.arenaBytes;
     const uint64_t grid = (std::min(outBytes, bound) + kCopyPiece - 1) / kCopyPiece + most;
-    hipLaunchKernelGGL(collect_copy_kernel, dim3((uint32_t)std::min<uint64_t>(grid, 0x7FFFFFFFull)), dim3(kBlock), 0, stream,
-                       R.arena, R.completed + std::min(first, R.queueCapacity), out, pitch, d_index, d_counts);
+    const dim3 blocks((uint32_t)std::min<uint64_t>(grid, 0x7FFFFFFFull));
+    // the first taken record: from the host, or from the cursor the plan has just moved
+    if (d_cursor)
+        hipLaunchKernelGGL(collect_next_copy_kernel, blocks, dim3(kBlock), 0, stream, R.arena, R.completed, d_cursor, out,
+                           pitch, d_index, d_counts);
+    else
+        hipLaunchKernelGGL(collect_copy_kernel, blocks, dim3(kBlock), 0, stream, R.arena,
+                           R.completed + std::min(first, R.queueCapacity), out, pitch, d_index, d_counts);
     return hipGetLastError();
 }
 
@@ -619,6 +630,24 @@ hipError_t launch_compact(const ReasDev &from, const ReasDev &to, hipStream_t st
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(reas_compact_kernel, dim3(from.tableSlots), dim3(kBlock), 0, stream, from, to);
     hipLaunchKernelGGL(reas_compact_finish, dim3(1), dim3(1), 0, stream, to);
+    return hipGetLastError();
+}
+
+hipError_t launch_turn(const ReasDev &R, const ReasDev &alt, uint32_t *d_cursor, const e2sar_hip_turn_marks &marks,
+                       uint64_t *d_status, void *moves, hipStream_t stream)
+{
+    static_assert(sizeof(TurnMove) == kTurnMoveBytes, "the move list is allocated by this size");
+    // four launches whatever the device decides; the grids come from tableSlots alone
+    const TurnMarks M{marks.arenaMark, marks.recordMark, marks.tableMark, marks.maxCarries};
+    TurnMove *mv = static_cast<TurnMove *>(moves);
+    const uint32_t tableGroups = cdiv(R.tableSlots, kBlock);
+    hipLaunchKernelGGL(turn_decide_kernel, dim3(std::min<uint32_t>(4u * tableGroups, 4096u)), dim3(kBlock), 0, stream, R,
+                       alt.slots, d_cursor, M, d_status);
+    hipLaunchKernelGGL(turn_out_kernel, dim3(tableGroups), dim3(kBlock), 0, stream, R, alt, M.maxCarries, mv, d_status);
+    hipLaunchKernelGGL(turn_copy_kernel, dim3(kTurnCopyGroups), dim3(kBlock), 0, stream, R.arena, alt.arena, R.ctl, mv,
+                       d_status);
+    hipLaunchKernelGGL(turn_back_kernel, dim3(tableGroups + kTurnCopyGroups), dim3(kBlock), 0, stream, alt, R, tableGroups,
+                       mv, d_cursor, d_status);
     return hipGetLastError();
 }
 

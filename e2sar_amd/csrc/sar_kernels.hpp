@@ -27,7 +27,7 @@ struct ReasSlot {
     uint32_t bvalid;     // 1 once bufOff/bytes are written
     unsigned long long acc;  // curBytes (low 36 bits) | numFragments (high 28 bits)
     uint64_t created;    // firstSegment, caller clock in ms
-    uint64_t pad1[2];
+    uint64_t pad1[2];    // [0]: turns the event was carried through (reas_turn.hpp); 0 in a claimed slot
 };
 static_assert(sizeof(ReasSlot) == 64, "slot is one 64-byte line");
 static_assert(offsetof(ReasSlot, eventNum) == 8 && offsetof(ReasSlot, bufOff) == 16 && offsetof(ReasSlot, bvalid) == 28,
@@ -52,8 +52,10 @@ struct ReasCtl {
     uint32_t errorFlags;
     unsigned long long compactTop;   // arena top of the destination arena during compaction
     uint32_t compactUsed;            // slots claimed in the destination table
+    uint32_t turnAged;               // events aged out by the turn in progress (reas_turn.hpp)
+    uint32_t turnMoves;              // ... and the survivors with bytes to move: entries of its move list
     uint32_t pad0;
-    uint64_t pad[2];
+    uint64_t pad;
     uint64_t pad2[6];
 };
 static_assert(sizeof(ReasCtl) % 128 == 0, "shards follow the control block on 128-byte lines");
@@ -252,10 +254,12 @@ hipError_t launch_seg_emit(const EmitSrc &S, const EmitNum &N, uint32_t maxEvent
                            e2sar_hip_seg_event *d_events, uint32_t *d_counts, uint32_t U, hipStream_t stream);
 // Completed records [first, ...) packed into out (pitch 0: ragged at `align`, else rows of
 // `pitch` bytes): the plan launch writes index / counts, the copy launch moves the bytes on
-// a grid sized from outBytes, maxEvents and the reassembler's capacities alone
+// a grid sized from outBytes, maxEvents and the reassembler's capacities alone.  d_cursor
+// (optional): a device word that stands for `first`, read when the plan runs and grown by
+// the n it took (e2sar_hip_reas_collect_next)
 hipError_t launch_collect(const ReasDev &R, uint32_t first, uint32_t maxEvents, uint8_t *out, uint64_t outBytes,
                           uint32_t pitch, uint32_t align, e2sar_hip_collect_rec *d_index, uint64_t *d_counts,
-                          hipStream_t stream);
+                          hipStream_t stream, uint32_t *d_cursor = nullptr);
 // The window of completed records [first, first + maxRecords) sorted, grouped and packed
 // into out (e2sar_hip_reas_build): work buffer bytes for a window (0 for one out of range);
 // the copy launch's grid from bounds alone (above 2^31 - 1: no launch is possible); and the
@@ -313,6 +317,14 @@ hipError_t launch_recycle(const ReasDev &R, bool dropCompleted, hipStream_t stre
 // Move every in-progress event of `from` (slots + arena bytes) into the empty `to`
 // table/arena (same ctl), then make `to`'s top and slot count current.
 hipError_t launch_compact(const ReasDev &from, const ReasDev &to, hipStream_t stream);
+// The turn (e2sar_hip_reas_turn): the device decides from marks, cursor and ReasCtl whether it
+// runs; if so the events in progress of R go through alt (the alternate table and arena, same
+// ctl) and back, aged by one carry, and everything else of R is cleared.  Four launches
+// whatever is decided; d_status: 4 device words; moves: the reassembler's move list,
+// kTurnMoveBytes per table slot.
+constexpr size_t kTurnMoveBytes = 32;
+hipError_t launch_turn(const ReasDev &R, const ReasDev &alt, uint32_t *d_cursor, const e2sar_hip_turn_marks &marks,
+                       uint64_t *d_status, void *moves, hipStream_t stream);
 size_t route_workspace_bytes(uint32_t n, uint32_t world);
 // one launch: reserve per-workgroup room in each destination's region (atomicAdd on
 // running[d]) and copy; datagrams past a region's cap are counted, not written

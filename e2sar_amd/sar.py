@@ -461,6 +461,43 @@ class DeviceReassembler(_Handle):
         self.collect(rows.view(-1), index, counts, first_record, max_events, pitch, stream=stream)
         return rows, index, counts
 
+    def new_cursor(self) -> torch.Tensor:
+        """A zeroed int32[1] on the device: the cursor of collect_next and turn."""
+        return torch.zeros(1, dtype=torch.int32, device=self.ctx.torch_device)
+
+    def collect_next(self, out: torch.Tensor, index: torch.Tensor, counts: torch.Tensor, cursor: torch.Tensor,
+                     max_events: Optional[int] = None, pitch: int = 0, align: int = 0,
+                     stream: Optional[torch.cuda.Stream] = None) -> None:
+        """collect() from the record `cursor[0]` names, read on the device when the launch
+        runs and left grown by the events taken (e2sar_hip_reas_collect_next): no host read,
+        capturable, each event delivered once.  `cursor`: new_cursor().  A reassembler
+        consumed this way is not polled."""
+        if out.dtype != torch.uint8 or index.dtype != torch.uint8 or counts.dtype != torch.int64:
+            raise ValueError("out and index are uint8 tensors, counts is int64")
+        if cursor.dtype != torch.int32 or cursor.numel() < 1 or cursor.device != out.device:
+            raise ValueError("cursor is an int32[1] tensor on the device of out")
+        if max_events is None:
+            max_events = index.numel() // COLLECT_REC_BYTES
+        if index.numel() < max_events * COLLECT_REC_BYTES or counts.numel() < 4:
+            raise ValueError("collect buffers too small")
+        _call("e2sar_hip_reas_collect_next", self._h, cursor.data_ptr(), max_events, out.data_ptr(), out.numel(), pitch,
+              align, index.data_ptr(), counts.data_ptr(), _s(stream))
+
+    def turn(self, cursor: torch.Tensor, status: torch.Tensor, arena_mark: int = 0, record_mark: int = 0,
+             table_mark: int = 0, max_carries: int = _capi.TURN_NEVER_LOST,
+             stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Upkeep decided on the device (e2sar_hip_reas_turn): once every record is collected
+        (cursor) and a mark is reached -- arena bytes in use, completed records, table slots
+        claimed; 0 is always reached -- the arena, the table and the completed list are
+        emptied except for the events in progress, which stay and complete later; one carried
+        max_carries times already is lost instead.  `status`: int64 device tensor, at least 4
+        entries: verdict (_capi.TURN_*), survivors, aged out, arena bytes in use.  No host
+        read, capturable; needs compactable=True."""
+        if cursor.dtype != torch.int32 or cursor.numel() < 1 or status.dtype != torch.int64 or status.numel() < 4:
+            raise ValueError("cursor is an int32[1] tensor, status an int64 tensor of at least 4")
+        marks = _capi.TurnMarks(int(arena_mark), int(record_mark), int(table_mark), int(max_carries), 0)
+        _call("e2sar_hip_reas_turn", self._h, cursor.data_ptr(), C.byref(marks), status.data_ptr(), _s(stream))
+
     @staticmethod
     def build_work_bytes(n: int) -> int:
         """Bytes of device scratch a build over a window of up to n records needs."""

@@ -413,6 +413,78 @@ int e2sar_hip_reas_collect(e2sar_hip_reas *r, uint32_t firstRecord, uint32_t max
                            e2sar_hip_collect_rec *d_index, uint64_t *d_counts, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* a receive graph that runs without end: reassemble_batch_dev -> collect_next -> turn,     */
+/* captured once, replayed over a stream whose events begin in one replay and end in a      */
+/* later one, with no host read.  collect_next is getEvent (e2sarDPReassembler.cpp:626-641) */
+/* behind a cursor the device keeps; turn is the upkeep a host loop does between batches -- */
+/* the poll + recycle/compact round trip of csrc/host/reassembler.cpp:504 and the GC pass   */
+/* of e2sarDPReassembler.cpp:236-291 -- decided and done on the device.                     */
+
+/* e2sar_hip_reas_collect with firstRecord = *d_cursor, a device uint32 the caller owns and */
+/* zeroes once: the plan launch reads it when it runs, and leaves it grown by d_counts[0].   */
+/* It does not move for a record that was not taken.  Everything else is collect's contract */
+/* to the letter, ragged and rows: the taken prefix, the bytes written and never written,   */
+/* d_counts[0..3], the statuses, two launches with no allocation, memset node or wait.      */
+/* outBytes == 0 takes nothing and leaves the cursor where it was; d_cursor == NULL is      */
+/* E2SAR_HIP_ERR_PARAMETER.                                                                  */
+/*   A host e2sar_hip_reas_poll slides the record list down, after which the cursor no      */
+/* longer means anything: a reassembler consumed through a cursor is not polled, unless the */
+/* caller re-zeroes the cursor after a poll that drained the list.  e2sar_hip_reas_turn      */
+/* zeroes it together with the list.  Asynchronous; may be captured into a HIP graph.       */
+int e2sar_hip_reas_collect_next(e2sar_hip_reas *r, uint32_t *d_cursor, uint32_t maxEvents,
+                                uint8_t *d_out, uint64_t outBytes, uint32_t pitch, uint32_t align,
+                                e2sar_hip_collect_rec *d_index, uint64_t *d_counts, void *stream);
+
+/* When a turn runs, and how long it carries an event in progress. */
+typedef struct e2sar_hip_turn_marks {
+    uint64_t arenaMark;    /* run when arena bytes in use >= this */
+    uint32_t recordMark;   /* ... or completed records stored >= this */
+    uint32_t tableMark;    /* ... or table slots ever claimed this epoch >= this */
+    uint32_t maxCarries;   /* an event already carried this many times is lost, not carried */
+    uint32_t reserved;     /* 0 */
+} e2sar_hip_turn_marks;
+
+/* Upkeep decided on the device when the launches run, that keeps the events in progress.   */
+/* d_status (device, 4 entries): [0] the verdict, [1] survivors carried, [2] events aged    */
+/* out, [3] arena bytes in use afterwards; a skipped turn leaves [1] = [2] = 0 and [3] the  */
+/* current use.                                                                              */
+/*   [0] = 2, skipped: *d_cursor < min(records completed, queueCapacity) -- a record has    */
+/* not been collected, and unconsumed records point into the arena, which must not move     */
+/* under them.  Nothing changes.                                                             */
+/*   [0] = 0, skipped: none of the marks is reached.  Nothing changes.  Arena bytes in use  */
+/* is the arena's top, above arenaBytes once it overflowed; tableMark compares against the  */
+/* live tableUsed of e2sar_hip_reas_get_stats.  A mark of 0 is always reached: all-zero     */
+/* marks run every time.                                                                     */
+/*   [0] = 1, ran.  Every event in progress carried fewer than maxCarries times is still in */
+/* progress -- key, length, bytes and fragments received, first-fragment time all kept, its */
+/* carry count one higher -- and later fragments complete it to the bytes a reassembler     */
+/* never turned would deliver; one created without a buffer (arena full) stays without, as  */
+/* e2sar_hip_reas_compact leaves it.  Every other event in progress is lost as the GC pass  */
+/* loses one: reassemblyLoss + 1, inProgress - 1, a lost record {eventNum, numFragments,    */
+/* dataId, enqueueLoss = 0} if the list has room; maxCarries = 0xFFFFFFFF never loses one.  */
+/* The completed list is empty and *d_cursor = 0; arena use is the survivors' lengths, each */
+/* rounded up to 256 (a zero length takes 256); tableUsed is their number, the entries of   */
+/* finished and lost events are gone.  The history counters, the per-datagram counters, the */
+/* lost list and errorFlags keep their values.  e2sar_hip_reas_arena() returns the base it  */
+/* returned before: a graph captured earlier, or holding the turn, still points at the      */
+/* right memory.                                                                             */
+/*   The carry count is the clock: now_ms is a host argument of every reassembly launch,    */
+/* frozen in a replayed graph, so a timeout against it would mean nothing there.  A caller  */
+/* who replays at a known cadence converts the timeout to turns; e2sar_hip_reas_gc still    */
+/* does GC by time outside graphs.                                                           */
+/*   E2SAR_HIP_ERR_PARAMETER for a NULL r, d_cursor, marks or d_status or a non-zero        */
+/* reserved; E2SAR_HIP_ERR_LOGIC for a reassembler created without                           */
+/* E2SAR_HIP_REAS_COMPACTABLE (the survivors pass through the alternate table and arena) or */
+/* with E2SAR_HIP_REAS_REFERENCE_ORDER (a key's slot is reused there for its next item,     */
+/* which a count per slot would age).  A failing call launches nothing.  Four launches      */
+/* whatever the device decides, grids from tableSlots alone; no allocation, no memset node, */
+/* no wait, no read-back: the call may be captured into a HIP graph.  A host                */
+/* e2sar_hip_reas_compact between the capture and a replay of any launch of this            */
+/* reassembler invalidates the graph, as it always did.  Asynchronous.                      */
+int e2sar_hip_reas_turn(e2sar_hip_reas *r, uint32_t *d_cursor, const e2sar_hip_turn_marks *marks,
+                        uint64_t *d_status /* device, 4 entries */, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* device-side event building: the completed records of one window, sorted by (eventNum,  */
 /* dataId) and grouped into built events -- every source's buffer for one eventNum side by */
 /* side, which is what a receiver behind an EJFAT load balancer works on.  The batch form */
