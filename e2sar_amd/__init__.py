@@ -5,7 +5,8 @@ Segmentation (reference src/e2sarDPSegmenter.cpp) and reassembly
 include/e2sar_hip.h.  Submodules:
 
   _capi      ctypes binding of the C ABI (loads e2sar_amd/lib/libe2sar_hip.so)
-  sar        device-level batch API (DeviceSegmenter / DeviceReassembler)
+  sar        device-level batch API (DeviceSegmenter / DeviceReassembler, and RowWindow:
+             reassembly straight into an [events, sources, pitch] tensor)
   dist       multi-GPU spread landing: routing into per-owner spans or regions (PacketRouter,
              RegionRouter), the all-to-all-v exchange, and SpreadPipeline, which overlaps
              the exchange with the landing of the next batch

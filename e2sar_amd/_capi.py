@@ -167,6 +167,36 @@ BUILD_MAX_RECORDS = 4096      # records one build call can look at
 BUILD_MAX_IDS = 64            # dataIds one build call can name
 
 
+class RowsCell(C.Structure):
+    """e2sar_hip_rows_cell: the state of one (event, source) of a rows window."""
+    _fields_ = [
+        ("acc", C.c_uint64),
+        ("bytes", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class Rows(C.Structure):
+    """e2sar_hip_rows: a rows window, device addresses and the host array of its dataIds."""
+    _fields_ = [
+        ("d_out", C.c_uint64),
+        ("d_cells", C.c_uint64),
+        ("d_base", C.c_uint64),
+        ("d_counts", C.c_uint64),
+        ("dataIds", C.POINTER(C.c_uint16)),
+        ("nIds", C.c_uint32),
+        ("nEvents", C.c_uint32),
+        ("pitch", C.c_uint32),
+        ("withLBHeader", C.c_int),
+    ]
+
+
+ROWS_MAX_IDS = 64
+ROWS_COMPLETE = 1             # RowsCell.flags: curBytes reached the event's length
+ROWS_TRUNCATED = 2            # ... a fragment passed the pitch
+ROWS_ACC_FRAG_SHIFT = 36      # RowsCell.acc: curBytes below, fragments above
+
+
 class LostRec(C.Structure):
     _fields_ = [
         ("eventNum", C.c_uint64),
@@ -203,6 +233,7 @@ assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
 assert C.sizeof(BuiltRec) == 32
 assert C.sizeof(TurnMarks) == 24
+assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 56
 
 vp = C.c_void_p
 i = C.c_int
@@ -247,6 +278,9 @@ SIGNATURES = {
     "e2sar_hip_segment_batch_dev": (i, [vp, vp, vp, u32, u32, i, u32, vp, u32, vp, vp]),
     "e2sar_hip_segment_batch_recycle": (i, [vp, vp, u32, u32, i, u32, i, vp, u32, vp, vp, i, vp]),
     "e2sar_hip_seg_emit": (i, [vp, C.POINTER(SegSource), C.POINTER(SegNumbering), u32, i, u32, vp, u32, u32, vp, vp, vp, vp]),
+    "e2sar_hip_rows_reassemble": (i, [vp, C.POINTER(Rows), vp, u32, vp, vp, u32, vp]),
+    "e2sar_hip_rows_advance": (i, [vp, C.POINTER(Rows), vp, u32, vp]),
+    "e2sar_hip_rows_clear": (i, [vp, C.POINTER(Rows), u64, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),
     "e2sar_hip_reas_collect": (i, [vp, u32, u32, vp, u64, u32, u32, vp, vp, vp]),
     "e2sar_hip_reas_collect_next": (i, [vp, vp, u32, vp, u64, u32, u32, vp, vp, vp]),

@@ -635,6 +635,77 @@ int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src, cons
     });
 }
 
+}  // extern "C"
+
+/* ---------------- reassembly straight into a tensor ---------------- */
+
+// What every call of the rows family checks first: the context and the descriptor.  Fills
+// the kernels' view of the window.
+static int check_rows(const e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, RowsDev &W)
+{
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (!w) return fail(E2SAR_HIP_ERR_PARAMETER, "rows descriptor is NULL");
+    if (!w->d_out || !w->d_cells || !w->d_base || !w->d_counts) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (!w->dataIds) return fail(E2SAR_HIP_ERR_PARAMETER, "dataIds is NULL");
+    if (w->nIds == 0 || w->nIds > E2SAR_HIP_ROWS_MAX_IDS) return fail(E2SAR_HIP_ERR_PARAMETER, "nIds must be 1..64");
+    for (uint32_t a = 0; a < w->nIds; a++)
+        for (uint32_t b = 0; b < a; b++)
+            if (w->dataIds[a] == w->dataIds[b]) return fail(E2SAR_HIP_ERR_PARAMETER, "dataIds must be distinct");
+    if (w->nEvents == 0 || (w->nEvents & (w->nEvents - 1u)))
+        return fail(E2SAR_HIP_ERR_PARAMETER, "nEvents must be a power of two");
+    if (w->pitch == 0 || (w->pitch & 255u)) return fail(E2SAR_HIP_ERR_PARAMETER, "pitch must be a multiple of 256");
+    if (int rc = check_pack_out(w->d_out)) return rc;
+    if (((uintptr_t)w->d_cells & 15u) || ((uintptr_t)w->d_base & 7u) || ((uintptr_t)w->d_counts & 7u))
+        return fail(E2SAR_HIP_ERR_PARAMETER, "cells must be 16-byte aligned, base and counts 8-byte aligned");
+    if ((uint64_t)w->nEvents * w->nIds > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "more than 2^32 - 1 cells");
+    W = RowsDev{};
+    W.out = w->d_out;
+    W.cells = w->d_cells;
+    W.base = w->d_base;
+    W.counts = w->d_counts;
+    W.nIds = w->nIds;
+    W.nEvents = w->nEvents;
+    W.pitch = w->pitch;
+    W.withLB = w->withLBHeader ? 1 : 0;
+    std::copy(w->dataIds, w->dataIds + w->nIds, W.ids);
+    return E2SAR_HIP_OK;
+}
+
+extern "C" {
+
+int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint8_t *d_packets, uint32_t stride,
+                              const uint32_t *d_lens, const uint32_t *d_count, uint32_t maxPackets, void *stream)
+{
+    RowsDev W;
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (!w || !d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL descriptor or device buffer");
+    if (int rc = check_rows(ctx, w, W)) return rc;
+    const uint32_t hl = W.withLB ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
+    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
+    if (int rc = check_packets(d_packets, stride, maxPackets)) return rc;
+    if (maxPackets == 0) return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "rows reassembly launch", [&](hipStream_t s) -> int {
+        if (rows_grid(maxPackets, stride) > 0x7FFFFFFFull)
+            return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "launch too large (workgroups of maxPackets)");
+        const hipError_t e = launch_rows(W, d_packets, stride, d_lens, d_count, maxPackets, s);
+        return e == hipSuccess ? E2SAR_HIP_OK : hip_fail(e, "rows reassembly launch");
+    });
+}
+
+int e2sar_hip_rows_advance(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint32_t *d_k, uint32_t kMax, void *stream)
+{
+    RowsDev W;
+    if (int rc = check_rows(ctx, w, W)) return rc;
+    return ctx_call(ctx, stream, "rows advance launch", [&](hipStream_t s) { return launch_rows_advance(W, d_k, kMax, s); });
+}
+
+int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t eventBase, void *stream)
+{
+    RowsDev W;
+    if (int rc = check_rows(ctx, w, W)) return rc;
+    return ctx_call(ctx, stream, "rows clear launch", [&](hipStream_t s) { return launch_rows_clear(W, eventBase, s); });
+}
+
 /* ---------------- reassembly ---------------- */
 
 int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, e2sar_hip_reas **out)

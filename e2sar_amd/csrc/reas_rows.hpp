@@ -1,0 +1,316 @@
+// reas_rows.hpp -- reassembly straight into a dense [events, sources, pitch] tensor (e2sar_hip_rows_*): no table, no arena.
+#pragma once
+
+#include "dev_access.hpp"
+#include "reas_classify.hpp"
+#include "reas_store.hpp"
+#include "wire.hpp"
+
+namespace e2sar_amd {
+
+// ---------------------------------------------------------------------------------
+// A stream that numbers its events consecutively and names its sources by dataId needs no
+// event table: the place of a fragment follows from its header alone -- row eventNum mod
+// nEvents, cell j where ids[j] == dataId, byte bufferOffset.  What is left of reas_kernel's
+// classification is one compare-and-swap per run head (the cell's length: whoever finds 0
+// opens the cell) and one add per run tail (the cell's accumulator); the copy is reas_kernel's.
+
+static_assert(sizeof(e2sar_hip_rows_cell) == 16 && offsetof(e2sar_hip_rows_cell, bytes) == 8 &&
+                  offsetof(e2sar_hip_rows_cell, flags) == 12,
+              "a cell is one 16-byte record: acc, bytes, flags");
+
+// counts[] of a window
+enum : uint32_t {
+    kRowsComplete = 0, kRowsAccepted = 1, kRowsBytes = 2, kRowsLate = 3, kRowsEarly = 4, kRowsForeign = 5,
+    kRowsBadHeader = 6, kRowsDataErr = 7, kRowsReleased = 8, kRowsReleasedComplete = 9
+};
+
+// The store windows of the copy start on this many 16-byte blocks (one 128-byte line), as
+// reas_kernel's do (kWinAlign there)
+constexpr uint32_t kRowsWinAlign = 8;
+
+// Per-workgroup LDS: destinations of the group's datagrams, and what the run tails need
+// after the copy (only the add's return value stays in a register meanwhile).
+struct RowsGroupLds {
+    PktInfo info[64];
+    uint32_t cell[64], bytes[64], rb[64], tail[64];
+    uint64_t cnt[8];               // the group's additions to counts[0..7] ([0]: known after the copy)
+};
+
+// The number of lanes of a whole wave for which `on` holds, added to counts[k] by the wave's
+// lane 0 -- no atomic when there is none.
+__device__ __forceinline__ void rows_count(uint64_t *counts, uint32_t k, bool on)
+{
+    const uint64_t m = __ballot(on);
+    if (m && (threadIdx.x & 63u) == 0u) atomicAdd((unsigned long long *)(counts + k), (unsigned long long)__builtin_popcountll(m));
+}
+
+// Classification of the group's datagrams by one whole wave (lane p: datagram p, `live`
+// below gn): the rules of e2sar_hip_rows_reassemble in their order.  Leaves every
+// datagram's destination in L.info, the run tails' state and the group's counts in L; returns
+// the value the tail's accumulator add found (consumed after the copy, rows_finish).
+__device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, const RawHdr &raw, uint32_t stride,
+                                                            bool live, RowsGroupLds &L)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
+    const ParsedHdr h = parse_hdr(raw, hl, stride, live);
+    bool ok = h.ok, derr = h.derr;
+
+    // the cell's column: the place of the dataId among the window's ids
+    uint32_t j = ~0u;
+    for (uint32_t k = 0; k < W.nIds; k++)
+        if ((uint32_t)W.ids[k] == h.d) j = k;
+    const bool foreign = ok && j == ~0u;
+    ok = ok && !foreign;
+    // the window, by 64-bit wrap-around distance from its base
+    const uint64_t dist = h.ev - *W.base;
+    const bool outside = ok && dist >= (uint64_t)W.nEvents;
+    const bool late = outside && (int64_t)dist < 0;
+    ok = ok && !outside;
+    // the fragment's own bounds: it opens nothing
+    if (ok && (h.blen == 0u || (uint64_t)h.off + h.pl > h.blen)) {
+        ok = false;
+        derr = true;
+    }
+    const uint32_t cell = ok ? ((uint32_t)h.ev & (W.nEvents - 1u)) * W.nIds + j : ~0u;
+
+    // ---- runs of one cell: consecutive lanes of one (eventNum, dataId) inside the window ----
+    const uint32_t pc = lane_prev(cell, ~0u), nc = lane_next(cell, ~0u);
+    const bool head = ok && (lane == 0u || pc != cell);
+    const bool tail = ok && (lane == 63u || nc != cell);
+    e2sar_hip_rows_cell *const cp = W.cells + (ok ? cell : 0u);
+
+    // the head opens the cell or learns its length: one compare-and-swap round trip per run
+    uint32_t sb = 0;
+    if (head) {
+        // (A load in front, so that only openers pay the compare-and-swap, lost: two round
+        // trips for them, and rows_kernel at MTU 1500 86.2 against 71.9 us)
+        const uint32_t was = atomicCAS(&cp->bytes, 0u, h.blen);
+        sb = was ? was : h.blen;
+    }
+    const int myhead = run_head_lane(__ballot(head), lane);
+    sb = __shfl(sb, myhead);
+
+    // bounds against the cell's length
+    bool take = ok;
+    if (take && (uint64_t)h.off + h.pl > sb) {
+        take = false;
+        derr = true;
+    }
+    // segmented sums over the run (inclusive scans, then the difference at the head)
+    const uint32_t xb = take ? h.pl : 0u, xc = take ? 1u : 0u;
+    const uint32_t ib = wave_incl_scan(xb), ic = wave_incl_scan(xc);
+    const uint32_t rb = ib - __shfl(ib - xb, myhead), rc = ic - __shfl(ic - xc, myhead);
+
+    // the tail's add: its return value is wanted only after the copy
+    unsigned long long old = 0;
+    const bool tailAdd = tail && rc > 0u;
+    if (tailAdd) old = atomicAdd((unsigned long long *)&cp->acc, ((unsigned long long)rc << kAccFragShift) | rb);
+    // a fragment that passes the pitch: rare, so one atomic each
+    const bool trunc = take && (uint64_t)h.off + h.pl > W.pitch;
+    if (trunc) atomicOr(&cp->flags, E2SAR_HIP_ROWS_TRUNCATED);
+
+    PktInfo pi;
+    const uint32_t room = (h.off < W.pitch) ? W.pitch - h.off : 0u;
+    pi.plen = take ? (h.pl < room ? h.pl : room) : 0u;
+    pi.dst = pi.plen ? (uint64_t)(W.out + (uint64_t)cell * W.pitch + h.off) : 0ull;
+    pi.hl = hl;
+    L.info[lane] = pi;
+    L.cell[lane] = cell;
+    L.bytes[lane] = sb;
+    L.rb[lane] = rb;
+    L.tail[lane] = tailAdd ? 1u : 0u;
+
+    // The workgroup's counts: this wave has classified all of its datagrams.  They wait in LDS
+    // until the copy is over (rows_finish): every workgroup of the launch adds to the same
+    // words, and vmcnt retires in order, so an add issued here would stand between this wave
+    // and the second round of its copy.
+    const uint32_t tl = take ? h.pl : 0u;                              // summed as 16-bit halves, as wave_stats does
+    const uint64_t tb = (uint64_t)readlane(wave_incl_scan(tl & 0xFFFFu), 63) +
+                        ((uint64_t)readlane(wave_incl_scan(tl >> 16), 63) << 16);
+    const uint64_t votes[8] = {0ull, __ballot(take), 0ull, __ballot(late), __ballot(outside && !late), __ballot(foreign),
+                               __ballot(h.bad), __ballot(derr)};
+    if (lane == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) L.cnt[k] = (uint64_t)__builtin_popcountll(votes[k]);
+        L.cnt[kRowsBytes] = tb;
+    }
+    return old;
+}
+
+// After the copy, by the classifying wave: a tail whose add of more than 0 bytes brought the
+// cell's curBytes to its length marks the cell complete.
+__device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long old, const RowsGroupLds &L)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t rb = L.rb[lane];
+    const bool done = L.tail[lane] && rb > 0u && (old & kAccBytesMask) + rb == (uint64_t)L.bytes[lane];
+    if (done) atomicOr(&W.cells[L.cell[lane]].flags, E2SAR_HIP_ROWS_COMPLETE);
+    // the workgroup's counts: lane k adds to counts[k], one instruction for all eight
+    const uint64_t ndone = (uint64_t)__builtin_popcountll(__ballot(done));
+    if (lane < 8u) {
+        const uint64_t v = (lane == kRowsComplete) ? ndone : L.cnt[lane];
+        if (v) atomicAdd((unsigned long long *)(W.counts + lane), (unsigned long long)v);
+    }
+}
+
+// One group of gn <= 64 consecutive datagrams [g0, g0 + gn), by the whole workgroup -- the
+// steps of reas_range (reas_fused.hpp), whose copy-round skeleton is restated here so that
+// kernel's code stays as it is:
+//   1. every wave loads the group's headers (lane p: datagram p);
+//   2. every thread issues its first U destination-aligned 16-byte payload loads -- the
+//      phase is bufferOffset mod 16: cells are 256-byte aligned;
+//   3. wave 0 classifies (rows_classify) while those loads are in flight;
+//   4. every thread stores its chunks (da_store), then loads and stores the rest round by
+//      round, the loads of round r + 1 issued before the stores of round r;
+//   5. wave 0's run tails mark completed cells (rows_finish).
+template <int U, int NT>
+__device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__restrict__ pkts, uint32_t stride,
+                                           const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn, RowsGroupLds &L)
+{
+    const uint32_t tx = threadIdx.x;
+    const bool w0 = tx < 64;
+    const uint32_t lane = tx & 63u;
+
+    ReasDev hdrOnly{};                                                  // load_hdr reads withLB alone
+    hdrOnly.withLB = W.withLB;
+    const RawHdr raw = load_hdr(hdrOnly, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
+
+    // Index space: datagram p owns S positions (spc + 14 rounded down to 8), its chunk c at
+    // p * S + f + c, f = its destination's 16-byte block within a 128-byte line, so every
+    // wave's 64 positions store whole 128-byte lines at both ends of its window.
+    const uint32_t spc = stride >> 4;
+    const uint32_t S = (spc + 2u * (kRowsWinAlign - 1u)) & ~(kRowsWinAlign - 1u);
+    const uint32_t nch = gn * S;
+    const float rS = 1.0f / (float)S;
+    const uint8_t *const bpk = pkts + (uint64_t)g0 * stride;
+    auto split_pos = [&](uint32_t i, uint32_t &p, uint32_t &j) {
+        const uint32_t ic = (i < nch) ? i : 0u;
+        p = div_recip(ic, S, rS);
+        j = ic - p * S;
+    };
+    const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
+    const uint32_t gPhase = bswap32(raw.re.y) & (16u * kRowsWinAlign - 1u);   // dst mod 128
+    const uint32_t gPlen = (raw.len >= hl) ? ((raw.len < stride) ? raw.len : stride) - hl : 0u;
+    auto issue = [&](uint32_t r0, u32x4(&xs)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t i = r0 + (uint32_t)u * NT + tx;
+            uint32_t p, j;
+            split_pos(i, p, j);
+            const uint32_t ph = __shfl(gPhase, (int)p), plen = __shfl(gPlen, (int)p);
+            const uint32_t a = ph & 15u, f = ph >> 4, c = j - f;
+            uint32_t off = 0, sh;
+            if (i < nch && j >= f && 16u * c < a + plen && (a & 3u) == 0u) off = p * stride + da_window(c, a, hl, stride, sh);
+            xs[u] = ld16(bpk + off);
+        }
+    };
+    auto store = [&](uint32_t r0, const u32x4(&xs)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t i = r0 + (uint32_t)u * NT + tx;
+            if (i >= nch) continue;
+            uint32_t p, j;
+            split_pos(i, p, j);
+            const PktInfo pi = L.info[p];
+            const uint32_t f = ((uint32_t)pi.dst >> 4) & (kRowsWinAlign - 1u);
+            if (j < f) continue;
+            da_store(pi, j - f, xs[u], bpk + (uint64_t)p * stride, stride);
+        }
+    };
+    u32x4 x[U], y[U];
+    issue(0u, x);                                                       // in flight while wave 0 classifies
+
+    unsigned long long old = 0;
+    if (w0) old = rows_classify(W, raw, stride, lane < gn, L);
+    lds_barrier();
+
+    constexpr uint32_t RS = (uint32_t)(NT * U);
+    if (RS < nch) issue(RS, y);
+    store(0u, x);
+    for (uint32_t r0 = RS; r0 < nch; r0 += 2 * RS) {
+        if (r0 + RS < nch) issue(r0 + RS, x);
+        store(r0, y);
+        if (r0 + RS >= nch) break;
+        if (r0 + 2 * RS < nch) issue(r0 + 2 * RS, y);
+        store(r0 + RS, x);
+    }
+
+    if (w0) rows_finish(W, old, L);
+}
+
+// rows_kernel: workgroup b takes datagrams [b*G, b*G + G) of the first n = min(*count,
+// bound) (count NULL: bound); the grid is cdiv(bound, G).  A workgroup at or past n costs the
+// load of one word and an exit (reas_devcount.hpp): no header load, no LDS, no counter.
+template <int U, int NT>
+__global__ __launch_bounds__(NT) void rows_kernel(RowsDev W, const uint8_t *__restrict__ pkts, uint32_t stride,
+                                                  const uint32_t *__restrict__ lens, const uint32_t *__restrict__ count,
+                                                  uint32_t bound, uint32_t G)
+{
+    __shared__ RowsGroupLds L;
+    uint32_t n = bound;
+    if (count) {
+        const uint32_t c = *count;
+        n = c < bound ? c : bound;
+    }
+    const uint64_t g0 = (uint64_t)blockIdx.x * G;
+    if (g0 >= n) return;
+    rows_range<U, NT>(W, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);
+}
+
+// ---------------------------------------------------------------------------------
+// the ring's upkeep
+
+// k = min(*d_k, kMax, nEvents): the events the window lets go of
+__device__ __forceinline__ uint32_t rows_advance_k(const RowsDev &W, const uint32_t *__restrict__ d_k, uint32_t kMax)
+{
+    uint32_t k = kMax < W.nEvents ? kMax : W.nEvents;
+    if (d_k) {
+        const uint32_t v = *d_k;
+        k = v < k ? v : k;
+    }
+    return k;
+}
+
+// Thread t < k * nIds: the cell of event base + t / nIds, source t % nIds, is counted
+// (released incomplete, released complete) and zeroed.  The base moves in a launch of its
+// own, after every workgroup here has read it.  Grid: cdiv(min(kMax, nEvents) * nIds, kBlock).
+__global__ __launch_bounds__(kBlock) void rows_release_kernel(RowsDev W, const uint32_t *__restrict__ d_k, uint32_t kMax)
+{
+    const uint64_t k = rows_advance_k(W, d_k, kMax);
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool in = t < k * W.nIds;
+    bool open = false, complete = false;
+    if (in) {
+        const uint64_t e = t / W.nIds;
+        const uint64_t c = ((*W.base + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + (t - e * W.nIds);
+        uint8_t *cp = reinterpret_cast<uint8_t *>(W.cells + c);
+        const u32x4 v = ld16(cp);
+        complete = (v.w & E2SAR_HIP_ROWS_COMPLETE) != 0u;
+        open = v.z != 0u && !complete;
+        st16(cp, u32x4{0u, 0u, 0u, 0u});
+    }
+    rows_count(W.counts, kRowsReleased, open);
+    rows_count(W.counts, kRowsReleasedComplete, complete);
+}
+
+__global__ __launch_bounds__(64) void rows_shift_kernel(RowsDev W, const uint32_t *__restrict__ d_k, uint32_t kMax)
+{
+    if (threadIdx.x == 0) *W.base += rows_advance_k(W, d_k, kMax);
+}
+
+// Every cell and all 16 counts zeroed, the base set: stores only, so it can be captured
+// where a memset node cannot.
+__global__ __launch_bounds__(kBlock) void rows_clear_kernel(RowsDev W, uint64_t eventBase)
+{
+    const uint64_t nCells = (uint64_t)W.nEvents * W.nIds;
+    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nCells; c += (uint64_t)gridDim.x * kBlock)
+        st16(reinterpret_cast<uint8_t *>(W.cells + c), u32x4{0u, 0u, 0u, 0u});
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < 16u) W.counts[threadIdx.x] = 0ull;
+        if (threadIdx.x == 16u) *W.base = eventBase;
+    }
+}
+
+}  // namespace e2sar_amd

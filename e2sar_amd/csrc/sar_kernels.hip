@@ -18,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
+// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_rows, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -33,6 +33,7 @@
 #include "reas_fused.hpp"
 #include "reas_split.hpp"
 #include "reas_devcount.hpp"
+#include "reas_rows.hpp"
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
 #include "reas_turn.hpp"
@@ -448,6 +449,80 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
             hipLaunchKernelGGL((reas_kernel<U, NT>), groups, dim3(NT), reas_lds<NT>(reas_kernel<U, NT>), stream, R, pkts,
                                stride, lens, n, now, G, (const uint32_t *)nullptr);
     });
+    return hipGetLastError();
+}
+
+// ---- rows family (reas_rows.hpp) ----
+
+// Workgroups of rows_kernel<U, NT> the current device holds at once (0 if unknown), per device.
+template <int U, int NT>
+static uint32_t rows_resident_groups()
+{
+    static std::atomic<uint32_t> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    uint32_t c = cache[dev].load(std::memory_order_relaxed);
+    if (c) return c;
+    int per = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rows_kernel<U, NT>, NT, 0) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per <= 0 || cus <= 0)
+        return 0;
+    c = (uint32_t)per * (uint32_t)cus;
+    cache[dev].store(c, std::memory_order_relaxed);
+    return c;
+}
+
+// Datagrams per rows_kernel workgroup for a launch sized for n: reas_kernel's rule
+// (reas_group_size), balanced over this kernel's residency.
+static uint32_t rows_group_size(uint32_t n, uint32_t stride)
+{
+    uint32_t G = 0;
+    with_reas_threads(stride, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        G = reas_group_size(n, stride, 0u, rows_resident_groups<kReasU, NT>);
+    });
+    return G;
+}
+
+uint64_t rows_grid(uint32_t maxPackets, uint32_t stride)
+{
+    if (maxPackets == 0) return 0;
+    const uint32_t G = rows_group_size(maxPackets, stride);
+    return ((uint64_t)maxPackets + G - 1u) / G;
+}
+
+hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                       const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream)
+{
+    constexpr int U = kReasU;
+    if (maxPackets == 0) return hipSuccess;
+    const uint32_t G = rows_group_size(maxPackets, stride);
+    const uint64_t grid = ((uint64_t)maxPackets + G - 1u) / G;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    with_reas_threads(stride, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((rows_kernel<U, NT>), dim3((uint32_t)grid), dim3(NT), reas_lds<NT>(rows_kernel<U, NT>), stream, W,
+                           pkts, stride, lens, d_count, maxPackets, G);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t kMax, hipStream_t stream)
+{
+    const uint64_t cells = (uint64_t)(kMax < W.nEvents ? kMax : W.nEvents) * W.nIds;     // <= 2^32 - 1
+    if (cells == 0) return hipSuccess;
+    hipLaunchKernelGGL(rows_release_kernel, dim3(cdiv(cells, kBlock)), dim3(kBlock), 0, stream, W, d_k, kMax);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_shift_kernel, dim3(1), dim3(64), 0, stream, W, d_k, kMax);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_clear(const RowsDev &W, uint64_t eventBase, hipStream_t stream)
+{
+    const uint64_t blocks = ((uint64_t)W.nEvents * W.nIds + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(rows_clear_kernel, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, stream, W,
+                       eventBase);
     return hipGetLastError();
 }
 

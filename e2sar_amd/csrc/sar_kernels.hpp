@@ -310,6 +310,26 @@ hipError_t launch_reas_scatter(const ReasDev &R, const uint8_t *pkts, uint32_t s
 hipError_t launch_reas_scatter_classify(const ReasDev &R, uint32_t stride, const uint8_t *spk, uint32_t sn,
                                         const void *swork, const uint8_t *cpk, const uint32_t *clens, uint32_t cn,
                                         uint64_t now, void *cwork, hipStream_t stream, bool nt);
+// The window of the rows family (e2sar_hip_rows), passed by value to its kernels: the ids
+// travel in the kernel arguments (128 bytes).
+struct RowsDev {
+    uint8_t *out;                  // [nEvents, nIds, pitch], 256-byte aligned
+    e2sar_hip_rows_cell *cells;    // [nEvents * nIds]
+    uint64_t *base;                // the window is eventNum in [*base, *base + nEvents)
+    uint64_t *counts;              // [16]
+    uint32_t nIds, nEvents, pitch;
+    int withLB;
+    uint16_t ids[E2SAR_HIP_ROWS_MAX_IDS];
+};
+// rows_kernel over n = min(*d_count, maxPackets) datagrams (d_count NULL: maxPackets): its
+// grid, from maxPackets and the stride alone (above 2^31 - 1: no launch is possible), and the
+// one launch
+uint64_t rows_grid(uint32_t maxPackets, uint32_t stride);
+hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                       const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream);
+// rows_release_kernel, then rows_shift_kernel; and rows_clear_kernel
+hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t kMax, hipStream_t stream);
+hipError_t launch_rows_clear(const RowsDev &W, uint64_t eventBase, hipStream_t stream);
 hipError_t launch_zero_words(void *p, uint64_t nWords, hipStream_t stream);   // p 4-byte aligned
 hipError_t launch_fill_bytes(void *p, int value, uint64_t n, hipStream_t stream); // any alignment
 hipError_t launch_gc(const ReasDev &R, uint64_t now, uint64_t timeout, hipStream_t stream);

@@ -646,6 +646,83 @@ class DeviceReassembler(_Handle):
         return _device_view(self.arena_ptr, self.arena_bytes, self.ctx.torch_device)
 
 
+# e2sar_hip_rows_cell: the state of one (event, source) of a RowWindow
+ROWS_CELL = np.dtype(_capi.RowsCell)
+ROWS_CELL_BYTES = ROWS_CELL.itemsize
+
+
+class RowWindow:
+    """Reassembles device-resident datagram batches straight into a dense
+    [n_events, n_ids, pitch] uint8 tensor (the e2sar_hip_rows_* family): the cell of a
+    fragment follows from its header alone -- row eventNum mod n_events, column j where
+    ids[j] == dataId, byte bufferOffset -- so there is no event table, no arena and no second
+    copy.  The window holds the events [base, base + n_events) and is a ring: advance() lets
+    the oldest go.  It owns `out`, `cells` (uint8, n_events * n_ids * ROWS_CELL_BYTES), `base`
+    (int64[1], read as uint64) and `counts` (int64[16]); nothing else is kept, here or in the
+    library.  Row bytes are never zeroed: a cell's `bytes` and flags say what of its row holds.
+    """
+
+    def __init__(self, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, event_base: int = 0,
+                 with_lb_header: bool = True):
+        ids = [int(d) for d in ids]
+        if not ids or len(ids) > _capi.ROWS_MAX_IDS:
+            raise ValueError("a RowWindow names 1..64 dataIds")
+        self.ctx = ctx
+        self.ids = ids
+        self.n_events = int(n_events)
+        self.pitch = int(pitch)
+        self.with_lb_header = with_lb_header
+        dev = ctx.torch_device
+        self.out = torch.empty((self.n_events, len(ids), self.pitch), dtype=torch.uint8, device=dev)
+        self.cells = torch.empty(self.n_events * len(ids) * ROWS_CELL_BYTES, dtype=torch.uint8, device=dev)
+        self.base = torch.empty(1, dtype=torch.int64, device=dev)
+        self.counts = torch.empty(16, dtype=torch.int64, device=dev)
+        self._ids = (C.c_uint16 * len(ids))(*ids)
+        self._w = _capi.Rows(self.out.data_ptr(), self.cells.data_ptr(), self.base.data_ptr(), self.counts.data_ptr(),
+                             self._ids, len(ids), self.n_events, self.pitch, 1 if with_lb_header else 0)
+        self.clear(event_base)
+
+    def reassemble(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, max_packets: int,
+                   count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """The first min(count[0], max_packets) datagrams of the batch -- max_packets when
+        `count` (an int32 device tensor, read as uint32 by the kernel) is omitted -- into the
+        window (e2sar_hip_rows_reassemble): one launch, no host read, capturable."""
+        if lens.dtype != torch.int32 or packets.dtype != torch.uint8 or (count is not None and count.dtype != torch.int32):
+            raise ValueError("packets is a uint8 tensor, lens and count are int32 tensors")
+        if count is not None and count.numel() < 1:
+            raise ValueError("count is empty")
+        _need_batch("packet batch buffers too small for max_packets", max_packets, stride, packets, lens)
+        _call("e2sar_hip_rows_reassemble", self.ctx.handle, C.byref(self._w), packets.data_ptr(), stride, lens.data_ptr(),
+              _p(count), max_packets, _s(stream))
+
+    def advance(self, k: int, count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Let go of the min(count[0], k, n_events) oldest events -- min(k, n_events) when
+        `count` (int32 device tensor) is omitted: their cells are counted (counts[8] released
+        incomplete, counts[9] complete) and zeroed, and the base moves on
+        (e2sar_hip_rows_advance).  No host read, capturable."""
+        if count is not None and (count.dtype != torch.int32 or count.numel() < 1):
+            raise ValueError("count is an int32 tensor of at least 1")
+        _call("e2sar_hip_rows_advance", self.ctx.handle, C.byref(self._w), _p(count), int(k), _s(stream))
+
+    def clear(self, event_base: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Every cell and count zeroed, the window at [event_base, event_base + n_events)
+        (e2sar_hip_rows_clear); row bytes stay."""
+        _call("e2sar_hip_rows_clear", self.ctx.handle, C.byref(self._w), int(event_base) & 0xFFFFFFFFFFFFFFFF, _s(stream))
+
+    def parse_cells(self) -> np.ndarray:
+        """The cells on the host, a ROWS_CELL array of shape [n_events, n_ids]: waits for the
+        device and copies."""
+        torch.cuda.synchronize(self.cells.device)
+        raw = self.cells.cpu().numpy().tobytes()
+        return np.frombuffer(raw, ROWS_CELL).reshape(self.n_events, len(self.ids)).copy()
+
+    def parse_counts(self):
+        """-> (the 16 counts, the base), as Python integers: waits for the device and copies."""
+        torch.cuda.synchronize(self.counts.device)
+        counts = [int(v) & 0xFFFFFFFFFFFFFFFF for v in self.counts.cpu().tolist()]
+        return counts, int(self.base.cpu().item()) & 0xFFFFFFFFFFFFFFFF
+
+
 class _CudaArray:
     def __init__(self, ptr: int, nbytes: int):
         self.__cuda_array_interface__ = {

@@ -652,6 +652,116 @@ int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src,
                        e2sar_hip_seg_event *d_events, uint32_t *d_counts, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* Reassembly straight into a tensor.  A stream that numbers its events consecutively    */
+/* (the Segmenter's default rule, e2sarDPSegmenter.cpp:901-948) and names its sources by  */
+/* dataId needs no event table, no arena and no second copy: the place of a fragment in a */
+/* dense [nEvents, nIds, pitch] byte tensor follows from its header alone -- row eventNum */
+/* mod nEvents, cell j where dataIds[j] == dataId, byte bufferOffset.  The family below   */
+/* is stateless, as e2sar_hip_seg_emit is: there is no e2sar_hip_reas object, every piece */
+/* of state is device memory the caller owns, and the descriptor is a host struct read    */
+/* when a call is made.  It replaces the per-packet body of the receive thread,           */
+/* e2sarDPReassembler.cpp:335-427 (header validation, eventsInProgress lookup and insert, */
+/* the memcpy at 391, the completion test at 403), the event queue behind it and -- with  */
+/* e2sar_hip_rows_advance -- the garbage collection of events that never complete         */
+/* (cpp:283-308).                                                                         */
+/*   The window is a ring: it holds the events eventNum in [*d_base, *d_base + nEvents),  */
+/* and e2sar_hip_rows_advance moves it on.  The chain producer -> e2sar_hip_seg_emit ->   */
+/* e2sar_hip_rows_reassemble -> consumer -> e2sar_hip_rows_advance is one capturable      */
+/* chain with no host read, and it runs without end.                                      */
+/*   A cell (16 bytes, 16-byte aligned) is the state of one (event, source): `acc` has    */
+/* the event table's accumulator layout, curBytes in the low 36 bits and the fragment     */
+/* count above; `bytes` is the event's length S, the bufferLength of the fragment that    */
+/* opened the cell (0 = empty: nothing arrived); `flags` says whether the cell is         */
+/* COMPLETE (curBytes reached S) and whether a fragment passed the pitch (TRUNCATED: its  */
+/* bytes past the pitch were dropped, but counted).  The cell of (eventNum, dataIds[j])   */
+/* is c = (eventNum & (nEvents - 1)) * nIds + j, its bytes start at d_out + c * pitch     */
+/* (64-bit arithmetic throughout).  The consumer reads `bytes` and `flags` of a cell and  */
+/* then the first min(bytes, pitch) bytes of its row; the rest of the row is never        */
+/* written and keeps what it held.                                                        */
+/*   d_counts (device u64[16], accumulating): [0] cells completed, [1] fragments          */
+/* accepted, [2] their payload bytes, [3] late (behind the window), [4] early (ahead of   */
+/* it), [5] foreign dataId, [6] bad header, [7] data error, [8] cells released incomplete */
+/* by advance, [9] cells released complete; [10..15] reserved, written only by clear.     */
+#define E2SAR_HIP_ROWS_MAX_IDS 64u
+#define E2SAR_HIP_ROWS_COMPLETE 1u
+#define E2SAR_HIP_ROWS_TRUNCATED 2u
+typedef struct e2sar_hip_rows_cell {   /* 16 bytes */
+    uint64_t acc;     /* curBytes (low 36 bits) | fragments << 36 */
+    uint32_t bytes;   /* the event's length S; 0 = empty */
+    uint32_t flags;   /* E2SAR_HIP_ROWS_COMPLETE, E2SAR_HIP_ROWS_TRUNCATED */
+} e2sar_hip_rows_cell;
+
+typedef struct e2sar_hip_rows {
+    uint8_t *d_out;               /* [nEvents, nIds, pitch] bytes, 256-byte aligned */
+    e2sar_hip_rows_cell *d_cells; /* [nEvents * nIds], 16-byte aligned */
+    uint64_t *d_base;             /* device u64: the window is eventNum in [base, base + nEvents) */
+    uint64_t *d_counts;           /* device u64[16], accumulating */
+    const uint16_t *dataIds;      /* host array, nIds distinct ids, 1..64 */
+    uint32_t nIds;
+    uint32_t nEvents;             /* power of two */
+    uint32_t pitch;               /* multiple of 256 */
+    int withLBHeader;
+} e2sar_hip_rows;
+
+/* The datagrams [0, n) of a batch into the window, n = min(*d_count, maxPackets), or     */
+/* maxPackets when d_count is NULL.  Slots and lengths: e2sar_hip_reassemble_batch's      */
+/* conventions.  One kernel launch, no allocation, no memset node, no wait and nothing    */
+/* read back: the call may be captured into a HIP graph.  The launch's geometry comes     */
+/* from maxPackets; no byte of a slot and no d_lens entry at or past n is read.           */
+/*   Per datagram, the first rule that applies:                                           */
+/*   1. header: the validation of e2sar_hip_reassemble_batch (cpp:340-357): a bad RE      */
+/*      version or a datagram too short for its headers -> counts[6]; a datagram longer   */
+/*      than its slot -> counts[7];                                                       */
+/*   2. a dataId that is not in dataIds -> counts[5];                                     */
+/*   3. window: d = eventNum - *d_base (64-bit wrap); d >= nEvents -> counts[3] (late)    */
+/*      when (int64_t)d < 0, else counts[4] (early);                                      */
+/*   4. own bounds: bufferLength == 0, or bufferOffset + payload > bufferLength (64 bits) */
+/*      -> counts[7]; such a fragment opens no cell;                                      */
+/*   5. the cell's length S is its `bytes` if that is not 0; otherwise this fragment      */
+/*      opens the cell with bytes = bufferLength (a compare-and-swap against 0: exactly   */
+/*      one opener wins).  bufferOffset + payload > S -> counts[7];                       */
+/*   6. accepted: payload bytes [0, min(payload, max(0, pitch - bufferOffset))) are       */
+/*      written at the cell's bufferOffset; bufferOffset + payload > pitch sets           */
+/*      TRUNCATED; acc grows by (payload, 1 fragment), the payload in full even where it  */
+/*      was cut; counts[1] += 1, counts[2] += payload; an add of more than 0 bytes that   */
+/*      brings curBytes to exactly S sets COMPLETE and adds 1 to counts[0].               */
+/* A datagram stopped by rules 1-5 writes nothing and touches no cell.  Never written:    */
+/* bytes of d_out outside the accepted fragments' (cut) extents, counts[8..15].           */
+/*   Consecutive datagrams of one cell may be added as one.  The result does not depend   */
+/* on the order of the datagrams nor on how a stream is cut into batches, provided no     */
+/* fragment arrives twice and each cell has one determinate opener within a launch (all   */
+/* its fragments in the launch announce one length, or the cell was opened by an earlier  */
+/* launch).  Unlike the reference, an offset-0 fragment is not special, a bufferLength of */
+/* 0 is a data error, and nothing is logged as lost: see e2sar_hip_rows_advance.          */
+/*   Flags and lengths are for launches ordered after this one.                           */
+/* Status: PARAMETER for a NULL ctx, w, d_packets or d_lens, a NULL d_out, d_cells,       */
+/* d_base, d_counts or dataIds, nIds 0 or above 64 or a repeated id, nEvents 0 or not a   */
+/* power of two, pitch 0 or not a multiple of 256, d_out not 256-byte aligned, d_cells    */
+/* not 16-byte or d_base / d_counts not 8-byte aligned, a stride or packet pointer        */
+/* e2sar_hip_reassemble_batch refuses; OUT_OF_RANGE when nEvents * nIds exceeds 2^32 - 1, */
+/* maxPackets * (stride / 16) exceeds 2^32 - 1 or the launch would exceed 2^31 - 1        */
+/* workgroups.  maxPackets == 0 succeeds with nothing launched; a failing call launches   */
+/* nothing.  Asynchronous.                                                                */
+int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint8_t *d_packets,
+                              uint32_t stride, const uint32_t *d_lens, const uint32_t *d_count,
+                              uint32_t maxPackets, void *stream);
+
+/* The ring's upkeep, decided on the device: k = min(*d_k, kMax, nEvents), or min(kMax,   */
+/* nEvents) when d_k is NULL.  For each of the k oldest events, base .. base + k - 1, and */
+/* every id: a cell with bytes != 0 and no COMPLETE adds 1 to counts[8] -- the loss a     */
+/* garbage-collection pass of the reference would log (cpp:283-308) -- a COMPLETE cell    */
+/* adds 1 to counts[9], and the cell is zeroed; row bytes are not touched.  Then *d_base  */
+/* += k (64-bit wrap).  k == 0 changes nothing.  Two launches, their grids from nEvents * */
+/* nIds and kMax alone; capturable as above.  Status: PARAMETER as above (ctx, w and the  */
+/* descriptor).  Asynchronous.                                                            */
+int e2sar_hip_rows_advance(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint32_t *d_k,
+                           uint32_t kMax, void *stream);
+
+/* Every cell and all 16 counts zeroed, *d_base = eventBase; row bytes are not touched.   */
+/* One launch of plain stores (no memset node), capturable.  Status as above.             */
+int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t eventBase, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* multi-GPU: events are owned by rank eventNum % world.  A rank that received       */
 /* (landed) datagrams of other ranks' events routes them: this packs the batch into */
 /* per-destination spans (stable order) and reports the span sizes, ready for one   */

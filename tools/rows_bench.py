@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Reassembly straight into a tensor against reassembly plus delivery.
+
+E events of B bytes are segmented on the device; then three ways of getting them out of the
+datagrams are timed with HIP events, alternating in one process after a warm-up
+(tools/ab_method.py), for a batch at each MTU of --mtus:
+
+  rows               e2sar_hip_rows_clear outside the clock, then one e2sar_hip_rows_reassemble
+                     into an [nEvents, 1, pitch] window, pitch = B rounded up to 256
+  reas+collect_rows  forced recycle outside the clock, then e2sar_hip_reassemble_batch and
+                     e2sar_hip_reas_collect in row mode at the same pitch: the same tensor, by
+                     way of the arena
+  reas               forced recycle outside the clock, then e2sar_hip_reassemble_batch alone
+
+Every form's output is compared with the events' source bytes once.
+
+  python tools/rows_bench.py [--events 205] [--event-bytes 1048576] [--mtus 1500,9000]
+                             [--reps 40] [--warmup 5] [--out FILE]
+Prints one JSON line (and writes it to --out).  Rates count payload bytes read + written once.
+"""
+import os
+
+import numpy as np
+
+import ab_method
+
+
+def batch(ctx, args, mtu, src, torch, sar):
+    dev = ctx.torch_device
+    E, B = args.events, args.event_bytes
+    base = 1 << 48
+    seg = sar.DeviceSegmenter(ctx, mtu=mtu, lb_hdr_version=2)
+    plan = seg.plan([(src[i].data_ptr(), B, base + i, 4321, 1 + i, base + i) for i in range(E)])
+    n = plan.total_packets
+    pk, ln = seg.alloc_packets(n)
+    seg.segment(plan, pk, ln)
+    n_events = 1
+    while n_events < E:
+        n_events <<= 1
+    pitch = (B + 255) // 256 * 256
+    win = sar.RowWindow(ctx, [4321], n_events, pitch, base, with_lb_header=True)
+    table = 1
+    while table < 8 * E:
+        table <<= 1
+    R = sar.DeviceReassembler(ctx, with_lb_header=True, table_slots=table, queue_capacity=E + 64, lost_capacity=64,
+                              arena_bytes=E * pitch + 4096)
+    rows = torch.zeros(E * pitch, dtype=torch.uint8, device=dev)
+    index = torch.zeros(E * sar.COLLECT_REC_BYTES, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def reas_collect():
+        R.reassemble(pk, seg.stride, ln, n)
+        R.collect(rows, index, counts, 0, E, pitch)
+
+    def recycle():
+        R.recycle(force=True)
+
+    forms = {
+        "rows": (lambda: win.reassemble(pk, seg.stride, ln, n), lambda: win.clear(base)),
+        "reas+collect_rows": (reas_collect, recycle),
+        "reas": (lambda: R.reassemble(pk, seg.stride, ln, n), recycle),
+    }
+
+    # every form's output against the source events
+    host = src[:, :B].cpu().numpy()
+    win.out.zero_()
+    win.clear(base)
+    forms["rows"][0]()
+    cells = win.parse_cells()[:, 0]
+    c, _ = win.parse_counts()
+    assert c[0] == E and c[1] == n and c[2] == E * B and not any(c[3:]), c
+    got = win.out[:, 0, :B].cpu().numpy()
+    for i in range(E):
+        r = (base + i) & (n_events - 1)
+        assert cells[r]["flags"] == 1 and cells[r]["bytes"] == B, (i, cells[r])
+        assert np.array_equal(got[r], host[i]), ("rows", i)
+    rows.zero_()
+    recycle()
+    reas_collect()
+    recs = sar.parse_collect(index, counts)
+    assert len(recs) == E, len(recs)
+    got = rows.view(E, pitch)[:, :B].cpu().numpy()
+    for k, r in enumerate(recs):
+        assert np.array_equal(got[k], host[int(r["eventNum"]) - base]), ("reas+collect_rows", k)
+    recycle()
+    forms["reas"][0]()
+    done = R.poll()
+    assert len(done) == E, len(done)
+    arena = R.arena_tensor()
+    for r in done[:: max(1, E // 8)]:
+        ev = arena[r.arenaOffset: r.arenaOffset + B].cpu().numpy()
+        assert r.bytes == B and np.array_equal(ev, host[r.eventNum - base]), ("reas", r.eventNum)
+
+    us = ab_method.measure(forms, args)
+    moved = {name: 2 * E * B for name in forms}
+    moved["reas+collect_rows"] = 4 * E * B
+    out = ab_method.summary(us, moved)
+    out["datagrams"] = n
+    R.close()
+    return out
+
+
+def main():
+    ap = ab_method.parser()
+    ap.add_argument("--mtus", default="1500,9000")
+    args = ap.parse_args()
+
+    import torch
+    from e2sar_amd import sar, _capi
+
+    ab_method.need_gpu("rows_bench")
+    dev = torch.device("cuda:0")
+    ctx = sar.Context(0)
+    E, B = args.events, args.event_bytes
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    src = torch.randint(0, 256, (E, (B + 255) // 256 * 256), dtype=torch.uint8, device=dev, generator=g)
+    result = {"tool": "rows_bench", "events": E, "event_bytes": B, "reps": args.reps,
+              "lib": os.path.basename(_capi.LIB_PATH), "device": torch.cuda.get_device_name(0), "mtu": {}}
+    for mtu in (int(m) for m in args.mtus.split(",")):
+        result["mtu"][str(mtu)] = batch(ctx, args, mtu, src, torch, sar)
+    ab_method.write_line(result, args.out)
+
+
+if __name__ == "__main__":
+    main()
