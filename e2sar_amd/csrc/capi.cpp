@@ -225,12 +225,17 @@ static int check_packets(const uint8_t *d_packets, uint32_t stride, uint32_t nPa
     return E2SAR_HIP_OK;
 }
 
-// A batch of nPackets datagram slots of `stride` bytes at d_packets, for reassembler r.
-static int check_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
+// A batch of nPackets datagram slots of `stride` bytes at d_packets for a reassembly, with or
+// without LB headers: the slot stride, then check_packets.
+static int check_slots(bool withLB, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
 {
-    const uint32_t hl = r->cfg.withLBHeader ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
+    const uint32_t hl = withLB ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
     if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
     return check_packets(d_packets, stride, nPackets);
+}
+static int check_batch(e2sar_hip_reas *r, const uint8_t *d_packets, uint32_t stride, uint32_t nPackets)
+{
+    return check_slots(r->cfg.withLBHeader != 0, d_packets, stride, nPackets);
 }
 
 // The caller's work buffer of a classified batch of n datagrams; tooSmall is the entry
@@ -680,9 +685,7 @@ int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const
     if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
     if (!w || !d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL descriptor or device buffer");
     if (int rc = check_rows(ctx, w, W)) return rc;
-    const uint32_t hl = W.withLB ? E2SAR_HIP_LBRE_HDR_LEN : E2SAR_HIP_RE_HDR_LEN;
-    if ((stride & 15u) || stride < hl + 16u) return fail(E2SAR_HIP_ERR_PARAMETER, "stride must be a multiple of 16 and > header + 16");
-    if (int rc = check_packets(d_packets, stride, maxPackets)) return rc;
+    if (int rc = check_slots(W.withLB != 0, d_packets, stride, maxPackets)) return rc;
     if (maxPackets == 0) return E2SAR_HIP_OK;
     return ctx_call(ctx, stream, "rows reassembly launch", [&](hipStream_t s) -> int {
         if (rows_grid(maxPackets, stride) > 0x7FFFFFFFull)

@@ -15,11 +15,12 @@ struct RawHdr {
     uint32_t re4;    // RE header dword 4 (eventNum low word)
 };
 
+// withLB: an LB header stands in front of the RE header
 template <bool HO = false>
-__device__ __forceinline__ RawHdr load_hdr(const ReasDev &R, const uint8_t *__restrict__ pkts, uint32_t stride,
+__device__ __forceinline__ RawHdr load_hdr(bool withLB, const uint8_t *__restrict__ pkts, uint32_t stride,
                                            const uint32_t *__restrict__ lens, uint32_t p)
 {
-    const uint8_t *re = pkts + (uint64_t)p * stride + (R.withLB ? kLBHdrLen : 0u);   // 16-byte aligned
+    const uint8_t *re = pkts + (uint64_t)p * stride + (withLB ? kLBHdrLen : 0u);   // 16-byte aligned
     RawHdr h;
     if (HO) {       // bytes handed off inside the launch (chained form): sc1 loads
         h.len = ld4_sc1(lens + p);

@@ -15,15 +15,8 @@ namespace e2sar_amd {
 // over the same device functions (reas_group, classify_wave_to_work, scatter_group), handed n
 // instead of the host's number; a workgroup whose group lies at or past n costs the load of
 // one word and an exit -- no header load, no LDS, no counter.  So no byte of a slot and no
-// length at or past n is read, and n = 0 leaves the reassembler as it was.
-
-// The batch's datagram count: one scalar load per workgroup (count is a kernel argument, so
-// the address and the value are wave-uniform), clamped to the bound the launch was sized for.
-__device__ __forceinline__ uint32_t dev_count(const uint32_t *__restrict__ count, uint32_t bound)
-{
-    const uint32_t c = *count;
-    return c < bound ? c : bound;
-}
+// length at or past n is read, and n = 0 leaves the reassembler as it was.  n is dev_count
+// (dev_access.hpp).
 
 // reas_kernel<U, NT> with the count read on the device: workgroup b reassembles datagrams
 // [b*G, b*G + G) of the first n; the grid is cdiv(bound, G).

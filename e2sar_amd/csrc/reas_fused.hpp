@@ -3,6 +3,7 @@
 
 #include "dev_access.hpp"
 #include "reas_classify.hpp"
+#include "reas_copy.hpp"
 #include "reas_store.hpp"
 #include "seg_device.hpp"
 #include "wire.hpp"
@@ -11,9 +12,6 @@ namespace e2sar_amd {
 
 // ---------------------------------------------------------------------------------
 // reassembly: one fused kernel
-
-// The fused kernel's store windows start on this many 16-byte blocks (one 128-byte line)
-constexpr uint32_t kWinAlign = 8;
 
 // Per-workgroup LDS of the fused reassembly: destinations of the group's datagrams, and
 // the run tails' completion state (only the atomic's return value stays in registers during
@@ -31,7 +29,8 @@ struct ReasGroupLds {
 //   3. wave 0 classifies (event table lookup/insert, run sums, counter atomics) while those
 //      loads are in flight, and leaves each datagram's destination in LDS;
 //   4. every thread stores its chunks (da_store), then loads and stores the rest round by
-//      round (U chunks of 16 bytes per thread per round);
+//      round (U chunks of 16 bytes per thread per round) -- 2 to 4 are group_copy
+//      (reas_copy.hpp), which rows_kernel shares;
 //   5. the run tails complete events (their atomic results are consumed last).
 // HO: the chained form -- every datagram byte and length is read with sc1 loads (they were
 // stored write-through by seg_block in the same launch).
@@ -46,77 +45,20 @@ __device__ __forceinline__ void reas_range(const ReasDev &R, const uint8_t *__re
 
     TRACE_AT(0, 0, trace_now());
     // every wave issues the (cached) header loads so no load result crosses a branch
-    const RawHdr raw = load_hdr<HO>(R, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
+    const RawHdr raw = load_hdr<HO>(R.withLB != 0, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
     TRACE_WAIT();
     TRACE_AT(2, 0, trace_now());
 
-    // Index space: datagram p owns S = spc + 14 rounded down to 8 positions, and its
-    // destination-aligned chunk c sits at position p * S + f + c, f = its destination's
-    // 16-byte block within a 128-byte line (dst mod 128 = bufferOffset mod 128: event
-    // buffers are 256-byte aligned).  Position ≡ destination block (mod 8), so every wave's
-    // 64 positions store whole 128-byte lines at both ends of its window.  With one position
-    // per chunk (S = spc), a window started and ended inside a line, the neighbouring
-    // window's store instruction wrote the rest later, and the non-temporal lines left L2 in
-    // between: 1.044x the payload in writes, 103 K partial write requests per launch; here
-    // 1.003x and 16 K (profiles/round6/window_align/: reas_kernel at MTU 9000 68.2-68.8 vs
-    // 69.9-70.8 us, at 1500 72.0-73.4 vs 72.8-74.6).  At MTU 1500 the padding costs no
-    // round: 59 datagrams fill 1.77 rounds of 3072 chunks at S = 92 and 2.0 at S = 104.
-    const uint32_t spc = stride >> 4;
-    const uint32_t S = (spc + 2u * (kWinAlign - 1u)) & ~(kWinAlign - 1u);
-    const uint32_t nch = gn * S;
-    const float rS = 1.0f / (float)S;
-    const uint8_t *const bpk = pkts + (uint64_t)g0 * stride;
-    const __amdgpu_buffer_rsrc_t bpkR = brsrc(bpk);                     // HO loads only
-    (void)bpkR;
-    // position i -> (datagram, position within its S); recomputed at store time rather than
-    // kept live across the classification (register pressure sets this kernel's occupancy)
-    auto split_pos = [&](uint32_t i, uint32_t &p, uint32_t &j) {
-        const uint32_t ic = (i < nch) ? i : 0u;
-        p = div_recip(ic, S, rS);
-        j = ic - p * S;
-    };
     const uint32_t hl = R.withLB ? kLBREHdrLen : kREHdrLen;
-    const uint32_t gPhase = bswap32(raw.re.y) & (16u * kWinAlign - 1u);   // dst mod 128
-    uint32_t gPlen = (raw.len >= hl) ? ((raw.len < stride) ? raw.len : stride) - hl : 0u;
+    const uint32_t gPhase = bswap32(raw.re.y) & kPhaseMask;
+    uint32_t gPlen = hdr_payload_len(raw.len, hl, stride);
     if (R.ownWorld > 1u && re_valid(raw.re.x) &&
         foreign_event(R, ((uint64_t)bswap32(raw.re.w) << 32) | bswap32(raw.re4)))
         gPlen = 0u;                                                    // another rank's: no payload loads
-    auto issue = [&](uint32_t r0, u32x4(&xs)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = r0 + (uint32_t)u * NT + tx;
-            uint32_t p, j;
-            split_pos(i, p, j);
-            const uint32_t ph = __shfl(gPhase, (int)p), plen = __shfl(gPlen, (int)p);
-            const uint32_t a = ph & 15u, f = ph >> 4, c = j - f;
-            uint32_t off = 0, sh;
-            if (i < nch && j >= f && 16u * c < a + plen && (a & 3u) == 0u) off = p * stride + da_window(c, a, hl, stride, sh);
-            xs[u] = HO ? ld16_sc1(bpkR, off) : ld16(bpk + off);
-        }
-    };
-    auto store = [&](uint32_t r0, const u32x4(&xs)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = r0 + (uint32_t)u * NT + tx;
-            if (i >= nch) continue;
-            uint32_t p, j;
-            split_pos(i, p, j);
-            const PktInfo pi = L.info[p];
-            const uint32_t f = ((uint32_t)pi.dst >> 4) & (kWinAlign - 1u);
-            if (j < f) continue;
-            da_store<HO>(pi, j - f, xs[u], bpk + (uint64_t)p * stride, stride);
-        }
-    };
-    u32x4 x[U], y[U];
-    // round 0 is in flight while wave 0 classifies.  (A/B, round 4: the first residency
-    // wave's groups classifying before their round-0 loads, so their claims do not queue
-    // behind 25 MB of loads, ran 0.5-2 us slower; round 1's loads in flight too -- the
-    // pipeline's second register set live across the classification -- cut occupancy and
-    // lost: DESIGN 4.5.)
-    issue(0u, x);
 
     unsigned long long old = 0;
-    if (w0) {
+    group_copy<U, HO, NT>(pkts, stride, g0, gn, hl, gPhase, gPlen, L.info, [&] {
+        if (!w0) return;                                               // wave 0 classifies
         const Classified cl = classify_wave<true>(R, raw, stride, lane < gn, now, g);
         L.info[lane] = cl.info;
         old = cl.old;
@@ -129,24 +71,7 @@ __device__ __forceinline__ void reas_range(const ReasDev &R, const uint8_t *__re
         L.rc[lane] = cl.rc;
         L.tail[lane] = cl.tailAdd ? 1u : 0u;
         TRACE_AT(0, 1, trace_now());
-    }
-    lds_barrier();
-    TRACE_AT(0, 2, trace_hwid());
-
-    // software pipeline: the loads of round r+1 are issued before the stores of round r.
-    // Loads, stores and atomics retire from vmcnt in issue order, so a load issued after
-    // a store can only be waited for together with that store's write acknowledgement;
-    // issued before it, round r+1's data is waited for while round r's stores drain.
-    constexpr uint32_t RS = (uint32_t)(NT * U);
-    if (RS < nch) issue(RS, y);
-    store(0u, x);
-    for (uint32_t r0 = RS; r0 < nch; r0 += 2 * RS) {
-        if (r0 + RS < nch) issue(r0 + RS, x);
-        store(r0, y);
-        if (r0 + RS >= nch) break;
-        if (r0 + 2 * RS < nch) issue(r0 + 2 * RS, y);
-        store(r0 + RS, x);
-    }
+    });
 
     if (w0 && L.tail[lane]) {
         Classified cl;

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(TB) void ro_key_kernel(ReasDev R, const uint8_t *__
         wgTag[i] = 0u;
         wgCnt[i] = 0u;
     }
-    const RawHdr raw = load_hdr(R, pkts, stride, lens, p);
+    const RawHdr raw = load_hdr(R.withLB != 0, pkts, stride, lens, p);
     const uint32_t hl = R.withLB ? kLBREHdrLen : kREHdrLen;
     const RoHdr rh = ro_parse_hdr(R, raw, hl, stride, live);
     ParsedHdr h = rh.h;

@@ -3,6 +3,7 @@
 
 #include "dev_access.hpp"
 #include "reas_classify.hpp"
+#include "reas_copy.hpp"
 #include "reas_store.hpp"
 #include "wire.hpp"
 
@@ -24,10 +25,6 @@ enum : uint32_t {
     kRowsComplete = 0, kRowsAccepted = 1, kRowsBytes = 2, kRowsLate = 3, kRowsEarly = 4, kRowsForeign = 5,
     kRowsBadHeader = 6, kRowsDataErr = 7, kRowsReleased = 8, kRowsReleasedComplete = 9
 };
-
-// The store windows of the copy start on this many 16-byte blocks (one 128-byte line), as
-// reas_kernel's do (kWinAlign there)
-constexpr uint32_t kRowsWinAlign = 8;
 
 // Per-workgroup LDS: destinations of the group's datagrams, and what the run tails need
 // after the copy (only the add's return value stays in a register meanwhile).
@@ -156,8 +153,7 @@ __device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long
 }
 
 // One group of gn <= 64 consecutive datagrams [g0, g0 + gn), by the whole workgroup -- the
-// steps of reas_range (reas_fused.hpp), whose copy-round skeleton is restated here so that
-// kernel's code stays as it is:
+// steps of reas_range (reas_fused.hpp) around the same group_copy (reas_copy.hpp):
 //   1. every wave loads the group's headers (lane p: datagram p);
 //   2. every thread issues its first U destination-aligned 16-byte payload loads -- the
 //      phase is bufferOffset mod 16: cells are 256-byte aligned;
@@ -169,73 +165,16 @@ template <int U, int NT>
 __device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__restrict__ pkts, uint32_t stride,
                                            const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn, RowsGroupLds &L)
 {
-    const uint32_t tx = threadIdx.x;
-    const bool w0 = tx < 64;
-    const uint32_t lane = tx & 63u;
+    const bool w0 = threadIdx.x < 64;
+    const uint32_t lane = threadIdx.x & 63u;
 
-    ReasDev hdrOnly{};                                                  // load_hdr reads withLB alone
-    hdrOnly.withLB = W.withLB;
-    const RawHdr raw = load_hdr(hdrOnly, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
-
-    // Index space: datagram p owns S positions (spc + 14 rounded down to 8), its chunk c at
-    // p * S + f + c, f = its destination's 16-byte block within a 128-byte line, so every
-    // wave's 64 positions store whole 128-byte lines at both ends of its window.
-    const uint32_t spc = stride >> 4;
-    const uint32_t S = (spc + 2u * (kRowsWinAlign - 1u)) & ~(kRowsWinAlign - 1u);
-    const uint32_t nch = gn * S;
-    const float rS = 1.0f / (float)S;
-    const uint8_t *const bpk = pkts + (uint64_t)g0 * stride;
-    auto split_pos = [&](uint32_t i, uint32_t &p, uint32_t &j) {
-        const uint32_t ic = (i < nch) ? i : 0u;
-        p = div_recip(ic, S, rS);
-        j = ic - p * S;
-    };
+    const RawHdr raw = load_hdr(W.withLB != 0, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
     const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
-    const uint32_t gPhase = bswap32(raw.re.y) & (16u * kRowsWinAlign - 1u);   // dst mod 128
-    const uint32_t gPlen = (raw.len >= hl) ? ((raw.len < stride) ? raw.len : stride) - hl : 0u;
-    auto issue = [&](uint32_t r0, u32x4(&xs)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = r0 + (uint32_t)u * NT + tx;
-            uint32_t p, j;
-            split_pos(i, p, j);
-            const uint32_t ph = __shfl(gPhase, (int)p), plen = __shfl(gPlen, (int)p);
-            const uint32_t a = ph & 15u, f = ph >> 4, c = j - f;
-            uint32_t off = 0, sh;
-            if (i < nch && j >= f && 16u * c < a + plen && (a & 3u) == 0u) off = p * stride + da_window(c, a, hl, stride, sh);
-            xs[u] = ld16(bpk + off);
-        }
-    };
-    auto store = [&](uint32_t r0, const u32x4(&xs)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = r0 + (uint32_t)u * NT + tx;
-            if (i >= nch) continue;
-            uint32_t p, j;
-            split_pos(i, p, j);
-            const PktInfo pi = L.info[p];
-            const uint32_t f = ((uint32_t)pi.dst >> 4) & (kRowsWinAlign - 1u);
-            if (j < f) continue;
-            da_store(pi, j - f, xs[u], bpk + (uint64_t)p * stride, stride);
-        }
-    };
-    u32x4 x[U], y[U];
-    issue(0u, x);                                                       // in flight while wave 0 classifies
 
     unsigned long long old = 0;
-    if (w0) old = rows_classify(W, raw, stride, lane < gn, L);
-    lds_barrier();
-
-    constexpr uint32_t RS = (uint32_t)(NT * U);
-    if (RS < nch) issue(RS, y);
-    store(0u, x);
-    for (uint32_t r0 = RS; r0 < nch; r0 += 2 * RS) {
-        if (r0 + RS < nch) issue(r0 + RS, x);
-        store(r0, y);
-        if (r0 + RS >= nch) break;
-        if (r0 + 2 * RS < nch) issue(r0 + 2 * RS, y);
-        store(r0 + RS, x);
-    }
+    group_copy<U, false, NT>(pkts, stride, g0, gn, hl, bswap32(raw.re.y) & kPhaseMask,
+                             hdr_payload_len(raw.len, hl, stride), L.info,
+                             [&] { if (w0) old = rows_classify(W, raw, stride, lane < gn, L); });
 
     if (w0) rows_finish(W, old, L);
 }
@@ -249,11 +188,7 @@ __global__ __launch_bounds__(NT) void rows_kernel(RowsDev W, const uint8_t *__re
                                                   uint32_t bound, uint32_t G)
 {
     __shared__ RowsGroupLds L;
-    uint32_t n = bound;
-    if (count) {
-        const uint32_t c = *count;
-        n = c < bound ? c : bound;
-    }
+    const uint32_t n = count ? dev_count(count, bound) : bound;
     const uint64_t g0 = (uint64_t)blockIdx.x * G;
     if (g0 >= n) return;
     rows_range<U, NT>(W, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);

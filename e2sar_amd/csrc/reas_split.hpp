@@ -31,7 +31,7 @@ __device__ __forceinline__ void classify_wave_to_work(const ReasDev &R, const ui
     const uint32_t p0 = wave * 64u;
     if (p0 >= n) return;                                       // wave-uniform
     const uint32_t gn = (n - p0 < 64u) ? n - p0 : 64u;
-    const RawHdr raw = load_hdr(R, pkts, stride, lens, p0 + ((lane < gn) ? lane : 0u));
+    const RawHdr raw = load_hdr(R.withLB != 0, pkts, stride, lens, p0 + ((lane < gn) ? lane : 0u));
     const Classified cl = classify_wave(R, raw, stride, lane < gn, now, wave);
     const bool done = completes(cl);
     if (lane < gn) st_info(info + p0 + lane, cl.info, done ? kPktCompletes : 0u);

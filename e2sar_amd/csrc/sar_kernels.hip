@@ -18,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_fused, reas_split, reas_devcount, reas_rows, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
+// reas_classify, reas_store, reas_copy, reas_fused, reas_split, reas_devcount, reas_rows, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -30,6 +30,7 @@
 #include "reas_table.hpp"
 #include "reas_classify.hpp"
 #include "reas_store.hpp"
+#include "reas_copy.hpp"
 #include "reas_fused.hpp"
 #include "reas_split.hpp"
 #include "reas_devcount.hpp"
@@ -113,9 +114,10 @@ static size_t occupancy_lds(K kernel, uint32_t perCU)
     return T - fa.sharedSizeBytes;
 }
 
-// Workgroups of reas_kernel<U, NT> the current device holds at once (0 if unknown), per device.
-template <int U, int NT>
-static uint32_t reas_resident_groups()
+// Workgroups of NT threads of Kernel the current device holds at once (0 if unknown); cached
+// per kernel and device.
+template <auto Kernel, int NT>
+static uint32_t resident_groups()
 {
     static std::atomic<uint32_t> cache[64];
     int dev = 0;
@@ -125,7 +127,7 @@ static uint32_t reas_resident_groups()
     int per = 0, cus = 0;
     // the uncapped occupancy, as the jumbo launch's cap was measured (balancing on the
     // capped one tied, profiles/round4/ab/reas_small_caps.log)
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reas_kernel<U, NT>, NT, 0) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, Kernel, NT, 0) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per <= 0 || cus <= 0)
         return 0;
     c = (uint32_t)per * (uint32_t)cus;
@@ -182,7 +184,7 @@ static bool seg_geom(uint32_t nEvents, uint32_t maxPacketsPerEvent, uint32_t str
     // 3383 -> 3007 groups for 2 x 1536 resident)
     const uint32_t target = std::min<uint32_t>(49u, std::max<uint32_t>(1u, kReasChunksPerBlock / spc));
     const uint32_t S0 = std::max<uint32_t>(1u, (uint32_t)((uint64_t)target * spc / g.unitChunks));
-    g.stripe = balance_waves(g.nUnits, S0, reas_resident_groups<kReasU, kBlock>(), 0xFFFFu);
+    g.stripe = balance_waves(g.nUnits, S0, resident_groups<reas_kernel<kReasU, kBlock>, kBlock>(), 0xFFFFu);
     return true;
 }
 
@@ -388,7 +390,7 @@ static uint32_t scatter_geometry(uint32_t stride, uint32_t n, uint32_t &blocks)
 }
 
 // fixedG: the reassembler's configured group size (e2sar_hip_reas_config.groupSize), 0 = auto;
-// resident: reas_resident_groups of the kernel that will run the groups
+// resident: resident_groups of the kernel that will run the groups
 static uint32_t reas_group_size(uint32_t n, uint32_t stride, uint32_t fixedG, uint32_t (*resident)())
 {
     if (fixedG) return fixedG < 64u ? fixedG : 64u;
@@ -440,7 +442,7 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
     if (n == 0) return hipSuccess;
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        const uint32_t G = reas_group_size(n, stride, R.groupSize, reas_resident_groups<U, NT>);
+        const uint32_t G = reas_group_size(n, stride, R.groupSize, resident_groups<reas_kernel<U, NT>, NT>);
         const dim3 groups(cdiv(n, G));
         if (d_count)
             hipLaunchKernelGGL((reas_dev_kernel<U, NT>), groups, dim3(NT), reas_lds<NT>(reas_dev_kernel<U, NT>), stream, R,
@@ -454,41 +456,21 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
 
 // ---- rows family (reas_rows.hpp) ----
 
-// Workgroups of rows_kernel<U, NT> the current device holds at once (0 if unknown), per device.
-template <int U, int NT>
-static uint32_t rows_resident_groups()
+// The launch's geometry for a bound of maxPackets: G datagrams per workgroup -- reas_kernel's
+// rule (reas_group_size), balanced over this kernel's residency; returns the grid.
+static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, uint32_t &G)
 {
-    static std::atomic<uint32_t> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    uint32_t c = cache[dev].load(std::memory_order_relaxed);
-    if (c) return c;
-    int per = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, rows_kernel<U, NT>, NT, 0) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per <= 0 || cus <= 0)
-        return 0;
-    c = (uint32_t)per * (uint32_t)cus;
-    cache[dev].store(c, std::memory_order_relaxed);
-    return c;
-}
-
-// Datagrams per rows_kernel workgroup for a launch sized for n: reas_kernel's rule
-// (reas_group_size), balanced over this kernel's residency.
-static uint32_t rows_group_size(uint32_t n, uint32_t stride)
-{
-    uint32_t G = 0;
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        G = reas_group_size(n, stride, 0u, rows_resident_groups<kReasU, NT>);
+        G = reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT>, NT>);
     });
-    return G;
+    return ((uint64_t)maxPackets + G - 1u) / G;
 }
 
 uint64_t rows_grid(uint32_t maxPackets, uint32_t stride)
 {
-    if (maxPackets == 0) return 0;
-    const uint32_t G = rows_group_size(maxPackets, stride);
-    return ((uint64_t)maxPackets + G - 1u) / G;
+    uint32_t G = 1;
+    return rows_geometry(maxPackets, stride, G);
 }
 
 hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
@@ -496,8 +478,8 @@ hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, c
 {
     constexpr int U = kReasU;
     if (maxPackets == 0) return hipSuccess;
-    const uint32_t G = rows_group_size(maxPackets, stride);
-    const uint64_t grid = ((uint64_t)maxPackets + G - 1u) / G;
+    uint32_t G = 1;
+    const uint64_t grid = rows_geometry(maxPackets, stride, G);
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
@@ -549,7 +531,7 @@ hipError_t launch_segreas(ChainBatches cb, int lbVersion, uint32_t maxPld, uint3
         const uint64_t chunks = (uint64_t)B.maxPacketsPerEvent * (stride >> 4);
         if (chunks > 0xFFFFFFFFull) return hipErrorInvalidValue;
         B.bpe = (B.nEvents && B.n) ? cdiv(chunks, (uint64_t)kBlock * kChainSegU) : 0u;
-        B.G = B.n ? reas_group_size(B.n, stride, R.groupSize, reas_resident_groups<U, kBlock>) : 1u;
+        B.G = B.n ? reas_group_size(B.n, stride, R.groupSize, resident_groups<reas_kernel<U, kBlock>, kBlock>) : 1u;
         B.start = (uint32_t)grid;
         B.nSeg = B.bpe * B.nEvents;
         grid += (uint64_t)B.nSeg + (B.n ? cdiv(B.n, B.G) : 0u);

@@ -26,8 +26,11 @@ KERNELS = {
     "collect_plan_kernel": 1, "collect_copy_kernel": 1, "emit_plan_kernel": 1, "seg_flat_kernel": 2,
     "build_plan_kernel": 1, "build_copy_kernel": 1,
     "reas_dev_kernel": 2, "reas_classify_dev_kernel": 1, "reas_scatter_dev_kernel": 6,
+    "rows_kernel": 2, "rows_release_kernel": 1, "rows_shift_kernel": 1, "rows_clear_kernel": 1,
+    "turn_decide_kernel": 1, "turn_out_kernel": 1, "turn_copy_kernel": 1, "turn_back_kernel": 1,
+    "collect_next_plan_kernel": 1, "collect_next_copy_kernel": 1,
 }
-assert sum(KERNELS.values()) == 49
+assert sum(KERNELS.values()) == 60
 
 
 def _remarks(src, tmp_path):

@@ -64,13 +64,15 @@ sub("""    const uint32_t spc = stride >> 4, budget = kReasChunksPerBlock;
     if (small) G = budget / spc < 64u ? (budget / spc ? budget / spc : 1u) : 64u;""")
 sub("""    if (fixedG) return fixedG < 64u ? fixedG : 64u;
 """, """    if (fixedG) return fixedG < 64u ? fixedG : 64u;
-    const bool small = resident == &reas_resident_groups<kReasUOne, kReasNTSmall>;
+    const bool small = resident == &resident_groups<reas_kernel<kReasUOne, kReasNTSmall>, kReasNTSmall>;
 """)
 sub("return balance_waves(n, G, resident(), 64u);",
     "return balance_waves(n, G, resident(), std::min<uint32_t>(64u, std::max<uint32_t>(1u, budget / spc)));")
-sub("""small ? reas_resident_groups<U, kReasNTSmall>""", """small ? reas_resident_groups<kReasUOne, kReasNTSmall>""")
-sub("""        hipLaunchKernelGGL((reas_kernel<U, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,""",
-    """        hipLaunchKernelGGL((reas_kernel<kReasUOne, kReasNTSmall>), dim3(groups), dim3(kReasNTSmall), 0, stream, R,""")
+# the small launch (launch_reassemble's lambda) takes the one-round U
+sub("""        constexpr int NT = decltype(nt)::value;
+        const uint32_t G = reas_group_size(n, stride, R.groupSize,""", """        constexpr int NT = decltype(nt)::value;
+        constexpr int U = NT == kReasNTSmall ? kReasUOne : kReasU;
+        const uint32_t G = reas_group_size(n, stride, R.groupSize,""")
 for f, s in texts.items():
     open(os.path.join(dst, f), "w").write(s)
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Iinclude", "-I" + dst,
