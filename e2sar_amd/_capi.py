@@ -197,6 +197,35 @@ ROWS_TRUNCATED = 2            # ... a fragment passed the pitch
 ROWS_ACC_FRAG_SHIFT = 36      # RowsCell.acc: curBytes below, fragments above
 
 
+class RowsReadyRule(C.Structure):
+    """e2sar_hip_rows_ready_rule: which events e2sar_hip_rows_ready takes as ready."""
+    _fields_ = [
+        ("requiredMask", C.c_uint64),
+        ("slack", C.c_uint32),
+        ("kMax", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class RowsEvent(C.Structure):
+    """e2sar_hip_rows_event: one ready event of a rows window."""
+    _fields_ = [
+        ("eventNum", C.c_uint64),
+        ("presentMask", C.c_uint64),
+        ("openMask", C.c_uint64),
+        ("row", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+ROWS_READY_ZERO = 1           # RowsReadyRule.flags: zero what the ready rows hold beyond their whole events
+ROWS_EV_COMPLETE = 1          # RowsEvent.flags: every required cell is COMPLETE
+ROWS_EV_GIVEN_UP = 2          # ... not complete, and `slack` or more events behind the horizon
+ROWS_EV_TRUNCATED = 4         # ... a cell of the event has ROWS_TRUNCATED
+ROWS_NEVER_GIVEN_UP = 0xFFFFFFFF  # RowsReadyRule.slack: wait for every event, however long
+
+
 class LostRec(C.Structure):
     _fields_ = [
         ("eventNum", C.c_uint64),
@@ -234,6 +263,7 @@ assert C.sizeof(CollectRec) == 32
 assert C.sizeof(BuiltRec) == 32
 assert C.sizeof(TurnMarks) == 24
 assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 56
+assert C.sizeof(RowsReadyRule) == 24 and C.sizeof(RowsEvent) == 32
 
 vp = C.c_void_p
 i = C.c_int
@@ -281,6 +311,8 @@ SIGNATURES = {
     "e2sar_hip_rows_reassemble": (i, [vp, C.POINTER(Rows), vp, u32, vp, vp, u32, vp]),
     "e2sar_hip_rows_advance": (i, [vp, C.POINTER(Rows), vp, u32, vp]),
     "e2sar_hip_rows_clear": (i, [vp, C.POINTER(Rows), u64, vp]),
+    "e2sar_hip_rows_ready_work_bytes": (sz, [u32]),
+    "e2sar_hip_rows_ready": (i, [vp, C.POINTER(Rows), C.POINTER(RowsReadyRule), vp, vp, vp, sz, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),
     "e2sar_hip_reas_collect": (i, [vp, u32, u32, vp, u64, u32, u32, vp, vp, vp]),
     "e2sar_hip_reas_collect_next": (i, [vp, vp, u32, vp, u64, u32, u32, vp, vp, vp]),

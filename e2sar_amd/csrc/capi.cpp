@@ -709,6 +709,33 @@ int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t e
     return ctx_call(ctx, stream, "rows clear launch", [&](hipStream_t s) { return launch_rows_clear(W, eventBase, s); });
 }
 
+size_t e2sar_hip_rows_ready_work_bytes(uint32_t nEvents) { return rows_ready_work_bytes(nEvents); }
+
+int e2sar_hip_rows_ready(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_ready_rule *rule, uint32_t *d_ready,
+                         e2sar_hip_rows_event *d_events, void *d_work, size_t workBytes, void *stream)
+{
+    RowsDev W;
+    if (int rc = check_rows(ctx, w, W)) return rc;
+    if (!rule) return fail(E2SAR_HIP_ERR_PARAMETER, "rule is NULL");
+    if (!d_ready || !d_work) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL device buffer");
+    if (rule->reserved != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "rule.reserved must be 0");
+    if (rule->flags & ~E2SAR_HIP_ROWS_READY_ZERO) return fail(E2SAR_HIP_ERR_PARAMETER, "unknown rule flags");
+    const uint64_t all = W.nIds == 64u ? ~0ull : (1ull << W.nIds) - 1ull;
+    if (rule->requiredMask & ~all) return fail(E2SAR_HIP_ERR_PARAMETER, "requiredMask names an id at or above nIds");
+    if (((uintptr_t)d_work & 255u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "work buffer not 256-byte aligned");
+    if (workBytes < rows_ready_work_bytes(W.nEvents)) return fail(E2SAR_HIP_ERR_PARAMETER, "ready work buffer too small");
+    if (((uintptr_t)d_ready & 3u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "d_ready not 4-byte aligned");
+    if (((uintptr_t)d_events & 7u) != 0) return fail(E2SAR_HIP_ERR_PARAMETER, "d_events not 8-byte aligned");
+    const bool zero = (rule->flags & E2SAR_HIP_ROWS_READY_ZERO) != 0;
+    if (zero && rows_zero_grid(W, rule->kMax) > 0x7FFFFFFFull)
+        return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "zero launch too large (8-KiB pieces of kMax x nIds cells)");
+    // no buffer of the library's, no memset node, no wait: the launches capture as they are
+    return ctx_call(ctx, stream, "rows ready launch", [&](hipStream_t s) {
+        return launch_rows_ready(W, rule->requiredMask ? rule->requiredMask : all, rule->slack, rule->kMax, zero, d_ready,
+                                 d_events, d_work, s);
+    });
+}
+
 /* ---------------- reassembly ---------------- */
 
 int e2sar_hip_reas_create(e2sar_hip_ctx *ctx, const e2sar_hip_reas_config *cfg, e2sar_hip_reas **out)

@@ -18,7 +18,7 @@
 // bytes and datagram bytes costs no shuffles.
 //
 // The device code sits in one header per subsystem (dev_access, seg_device, reas_table,
-// reas_classify, reas_store, reas_copy, reas_fused, reas_split, reas_devcount, reas_rows, reas_order, reas_upkeep, reas_turn, reas_collect, reas_build, seg_emit, route), all
+// reas_classify, reas_store, reas_copy, reas_fused, reas_split, reas_devcount, reas_rows, reas_order, reas_upkeep, reas_rows_ready, reas_turn, reas_collect, reas_build, seg_emit, route), all
 // compiled into this one translation unit (the build has no relocatable device code:
 // seg_kernel calls recycle_slots, and the E2SAR_TRACE builds share one g_trace array); below
 // them, the host launchers and their launch geometry.
@@ -37,6 +37,7 @@
 #include "reas_rows.hpp"
 #include "reas_order.hpp"
 #include "reas_upkeep.hpp"
+#include "reas_rows_ready.hpp"
 #include "reas_turn.hpp"
 #include "reas_collect.hpp"
 #include "reas_build.hpp"
@@ -497,6 +498,31 @@ hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t k
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rows_shift_kernel, dim3(1), dim3(64), 0, stream, W, d_k, kMax);
+    return hipGetLastError();
+}
+
+// min(kMax, nEvents) * nIds * ceil(pitch / kCopyPiece): the workgroups of rows_zero_kernel
+uint64_t rows_zero_grid(const RowsDev &W, uint32_t kMax)
+{
+    return (uint64_t)(kMax < W.nEvents ? kMax : W.nEvents) * W.nIds * (((uint64_t)W.pitch + kCopyPiece - 1u) / kCopyPiece);
+}
+
+size_t rows_ready_work_bytes(uint32_t nEvents) { return rows_ready_work_size(nEvents); }
+
+hipError_t launch_rows_ready(const RowsDev &W, uint64_t required, uint32_t slack, uint32_t kMax, bool zero, uint32_t *d_ready,
+                             e2sar_hip_rows_event *d_events, void *d_work, hipStream_t stream)
+{
+    const uint64_t pieces = zero ? rows_zero_grid(W, kMax) : 0;
+    if (pieces > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rows_scan_kernel, dim3(cdiv(W.nEvents, kBlock)), dim3(kBlock), 0, stream, W, d_work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_ready_kernel, dim3(1), dim3(kBlock), 0, stream, W, RowsRule{required, slack, kMax}, d_work, d_ready,
+                       d_events);
+    e = hipGetLastError();
+    if (e != hipSuccess || pieces == 0) return e;
+    hipLaunchKernelGGL(rows_zero_kernel, dim3((uint32_t)pieces), dim3(kBlock), 0, stream, W, (const uint32_t *)d_ready,
+                       (uint32_t)(((uint64_t)W.pitch + kCopyPiece - 1u) / kCopyPiece));
     return hipGetLastError();
 }
 

@@ -330,6 +330,13 @@ hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, c
 // rows_release_kernel, then rows_shift_kernel; and rows_clear_kernel
 hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t kMax, hipStream_t stream);
 hipError_t launch_rows_clear(const RowsDev &W, uint64_t eventBase, hipStream_t stream);
+// e2sar_hip_rows_ready: rows_scan_kernel, rows_ready_kernel and, with `zero`, rows_zero_kernel, whose grid
+// (rows_zero_grid, from the descriptor and kMax alone) must not exceed 2^31 - 1; `required` is not 0; d_work holds
+// rows_ready_work_bytes(nEvents)
+uint64_t rows_zero_grid(const RowsDev &W, uint32_t kMax);
+size_t rows_ready_work_bytes(uint32_t nEvents);
+hipError_t launch_rows_ready(const RowsDev &W, uint64_t required, uint32_t slack, uint32_t kMax, bool zero, uint32_t *d_ready,
+                             e2sar_hip_rows_event *d_events, void *d_work, hipStream_t stream);
 hipError_t launch_zero_words(void *p, uint64_t nWords, hipStream_t stream);   // p 4-byte aligned
 hipError_t launch_fill_bytes(void *p, int value, uint64_t n, hipStream_t stream); // any alignment
 hipError_t launch_gc(const ReasDev &R, uint64_t now, uint64_t timeout, hipStream_t stream);

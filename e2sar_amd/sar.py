@@ -649,6 +649,9 @@ class DeviceReassembler(_Handle):
 # e2sar_hip_rows_cell: the state of one (event, source) of a RowWindow
 ROWS_CELL = np.dtype(_capi.RowsCell)
 ROWS_CELL_BYTES = ROWS_CELL.itemsize
+# e2sar_hip_rows_event: one ready event of RowWindow.ready
+ROWS_EVENT = np.dtype(_capi.RowsEvent)
+ROWS_EVENT_BYTES = ROWS_EVENT.itemsize
 
 
 class RowWindow:
@@ -659,7 +662,10 @@ class RowWindow:
     copy.  The window holds the events [base, base + n_events) and is a ring: advance() lets
     the oldest go.  It owns `out`, `cells` (uint8, n_events * n_ids * ROWS_CELL_BYTES), `base`
     (int64[1], read as uint64) and `counts` (int64[16]); nothing else is kept, here or in the
-    library.  Row bytes are never zeroed: a cell's `bytes` and flags say what of its row holds.
+    library.  Row bytes are never zeroed by these: a cell's `bytes` and flags say what of its row
+    holds.  alloc_ready() and ready() add the delivery half: which of the oldest events are whole or
+    given up is decided on the device, their rows are zero-filled on request, and the count goes
+    to advance() as a device word.
     """
 
     def __init__(self, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, event_base: int = 0,
@@ -708,6 +714,45 @@ class RowWindow:
         """Every cell and count zeroed, the window at [event_base, event_base + n_events)
         (e2sar_hip_rows_clear); row bytes stay."""
         _call("e2sar_hip_rows_clear", self.ctx.handle, C.byref(self._w), int(event_base) & 0xFFFFFFFFFFFFFFFF, _s(stream))
+
+    def alloc_ready(self, k_max: int) -> None:
+        """Give the window what ready() writes: `ready` (int32[8], read as uint32), `events`
+        (uint8, k_max * ROWS_EVENT_BYTES) and the call's work buffer."""
+        dev = self.out.device
+        self.k_max = int(k_max)
+        self.ready_words = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.events = torch.zeros(self.k_max * ROWS_EVENT_BYTES, dtype=torch.uint8, device=dev)
+        self.ready_work = torch.empty(int(lib().e2sar_hip_rows_ready_work_bytes(self.n_events)), dtype=torch.uint8, device=dev)
+
+    def ready(self, slack: int, k_max: Optional[int] = None, required: Optional[Sequence[int]] = None, zero: bool = False,
+              stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Decide on the device which of the oldest events are ready (e2sar_hip_rows_ready): an
+        event whose `required` dataIds (default: all) are complete, or one that an event
+        `slack` or more newer has overtaken (_capi.ROWS_NEVER_GIVEN_UP: none), up to the first
+        that is neither and at most k_max (default: alloc_ready's).  Writes `ready_words` --
+        k, complete, given up, horizon, complete cells, open incomplete cells -- and the k
+        records of `events`; with `zero`, the k rows hold zeros wherever they do not hold a
+        whole event.  advance(k_max, count=ready_words[0:1]) lets the k events go.  No host
+        read, capturable; parse_ready reads the result back."""
+        if not hasattr(self, "ready_words"):
+            raise ValueError("alloc_ready(k_max) comes first")
+        k_max = self.k_max if k_max is None else int(k_max)
+        if min(k_max, self.n_events) > self.k_max:
+            raise ValueError("more events than alloc_ready made room for")
+        mask = 0
+        for d in required or ():
+            mask |= 1 << self.ids.index(int(d))
+        rule = _capi.RowsReadyRule(mask, int(slack), k_max, _capi.ROWS_READY_ZERO if zero else 0, 0)
+        _call("e2sar_hip_rows_ready", self.ctx.handle, C.byref(self._w), C.byref(rule), self.ready_words.data_ptr(),
+              self.events.data_ptr() if self.events.numel() else 0, self.ready_work.data_ptr(), self.ready_work.numel(), _s(stream))
+
+    def parse_ready(self):
+        """-> (the 8 words ready() wrote, a ROWS_EVENT array of its k records): waits for the
+        device and copies."""
+        torch.cuda.synchronize(self.ready_words.device)
+        words = [int(v) & 0xFFFFFFFF for v in self.ready_words.cpu().tolist()]
+        raw = self.events[: words[0] * ROWS_EVENT_BYTES].cpu().numpy().tobytes()
+        return words, np.frombuffer(raw, ROWS_EVENT).copy()
 
     def parse_cells(self) -> np.ndarray:
         """The cells on the host, a ROWS_CELL array of shape [n_events, n_ids]: waits for the

@@ -761,6 +761,77 @@ int e2sar_hip_rows_advance(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const ui
 /* One launch of plain stores (no memset node), capturable.  Status as above.             */
 int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t eventBase, void *stream);
 
+/* Which events are ready, decided on the device: the k that e2sar_hip_rows_advance takes,    */
+/* so that e2sar_hip_rows_reassemble -> e2sar_hip_rows_ready -> consumer ->                  */
+/* e2sar_hip_rows_advance(d_k = d_ready) is the chain above with no host read.  The batch    */
+/* form of the reference's delivery of whole events and of its garbage collection by         */
+/* eventTimeout_ms (e2sarDPReassembler.cpp:236-291), for a stream numbered consecutively:    */
+/* the clock is distance in event numbers, not time, for the reason e2sar_hip_reas_turn      */
+/* gives for its carry count -- a now_ms is frozen in a replayed graph.                      */
+/*   Let N = nEvents, B = *d_base and i in [0, N): event i is B + i (64-bit wrap), its row   */
+/* (B + i) & (N - 1); open(i) are the ids whose cell has bytes != 0, present(i) those whose  */
+/* cell is COMPLETE; R = requiredMask, or all nIds bits when that is 0.  The horizon H is 0  */
+/* when no cell of the window is open, else 1 + the largest i with an open cell.  Per event, */
+/* the first rule that applies:                                                              */
+/*   1. complete: present(i) & R == R;                                                       */
+/*   2. given up: i < H and H - 1 - i >= slack -- an event `slack` or more newer has opened  */
+/*      a cell (slack 0: every event behind the horizon; 0xFFFFFFFF: never);                 */
+/*   3. otherwise the event is waited for.                                                   */
+/* k = min(kMax, N, the first i that is waited for).                                         */
+/*   d_ready (device u32[8]): [0] k -- &d_ready[0] is e2sar_hip_rows_advance's d_k; [1] the  */
+/* complete events among the k; [2] the given-up ones; [3] H; [4] the cells of the k events  */
+/* that are COMPLETE, over all ids and not only R; [5] their cells that are open and not     */
+/* COMPLETE; [6], [7] 0.                                                                     */
+/*   d_events (device, min(kMax, N) records, or NULL: only the counts are written):          */
+/* d_events[i], i < k, describes event B + i, in event order; `flags` has COMPLETE or        */
+/* GIVEN_UP, and TRUNCATED when a cell of the event has E2SAR_HIP_ROWS_TRUNCATED.  The       */
+/* event's cells start at row * nIds, its bytes at d_out + row * nIds * pitch.               */
+/*   With E2SAR_HIP_ROWS_READY_ZERO, for every i < k and every j < nIds, required or not: a  */
+/* COMPLETE cell gets bytes [min(bytes, pitch), pitch) of its row set to 0, any other cell   */
+/* [0, pitch): the k rows are then exactly the bytes of whole events with zeros elsewhere, a */
+/* dense tensor.  Without the flag d_out is not touched.                                     */
+/*   Never written: the cells, *d_base and d_counts -- two calls with no reassembly between  */
+/* them give the same answer, and advance still counts the released cells in counts[8] and   */
+/* counts[9]; d_events entries at or past k; bytes of d_out other than those named above.    */
+/*   The result describes the window as the launches ordered before this call left it: the   */
+/* caller orders it after its e2sar_hip_rows_reassemble, and e2sar_hip_rows_advance before   */
+/* the next one.  Two launches, three with the flag, their grids from the descriptor and     */
+/* kMax alone; no allocation, no memset node, no wait and nothing read back: capturable.     */
+/* d_work is the caller's, 256-byte aligned, at least e2sar_hip_rows_ready_work_bytes(N); it */
+/* needs no initialisation and is free once the call has run.                                */
+/* Status: e2sar_hip_rows_advance's (ctx, w and the descriptor); PARAMETER for a NULL rule,  */
+/* d_ready or d_work, a reserved that is not 0, unknown flags, requiredMask bits at or above */
+/* nIds, a work buffer that is too small or not 256-byte aligned, a d_ready that is not      */
+/* 4-byte or a d_events that is not 8-byte aligned; OUT_OF_RANGE when the flag's launch      */
+/* would exceed 2^31 - 1 workgroups (8-KiB pieces of min(kMax, N) * nIds cells).  kMax == 0  */
+/* succeeds, writes d_ready with k = 0 and H, and zeroes nothing; a failing call launches    */
+/* nothing.  Asynchronous.                                                                   */
+#define E2SAR_HIP_ROWS_READY_ZERO   1u          /* rule.flags */
+#define E2SAR_HIP_ROWS_EV_COMPLETE  1u          /* e2sar_hip_rows_event.flags */
+#define E2SAR_HIP_ROWS_EV_GIVEN_UP  2u
+#define E2SAR_HIP_ROWS_EV_TRUNCATED 4u          /* some cell of the event has TRUNCATED */
+
+typedef struct e2sar_hip_rows_ready_rule {
+    uint64_t requiredMask; /* bit j: dataIds[j] must be COMPLETE; 0 = all nIds */
+    uint32_t slack;        /* give an event up once an event this many or more newer has opened a cell; 0xFFFFFFFF: never */
+    uint32_t kMax;         /* at most this many events */
+    uint32_t flags;        /* E2SAR_HIP_ROWS_READY_ZERO */
+    uint32_t reserved;     /* 0 */
+} e2sar_hip_rows_ready_rule;
+
+typedef struct e2sar_hip_rows_event {   /* 32 bytes */
+    uint64_t eventNum;
+    uint64_t presentMask;  /* bit j: cell (event, dataIds[j]) is COMPLETE */
+    uint64_t openMask;     /* bit j: cell's bytes != 0 */
+    uint32_t row;          /* eventNum & (nEvents - 1): its cells start at row * nIds */
+    uint32_t flags;
+} e2sar_hip_rows_event;
+
+size_t e2sar_hip_rows_ready_work_bytes(uint32_t nEvents);
+int e2sar_hip_rows_ready(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_ready_rule *rule,
+                         uint32_t *d_ready /* device u32[8] */, e2sar_hip_rows_event *d_events /* device [min(kMax, nEvents)], or NULL */,
+                         void *d_work, size_t workBytes, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* multi-GPU: events are owned by rank eventNum % world.  A rank that received       */
 /* (landed) datagrams of other ranks' events routes them: this packs the batch into */
