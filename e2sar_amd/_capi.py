@@ -188,6 +188,8 @@ class Rows(C.Structure):
         ("nEvents", C.c_uint32),
         ("pitch", C.c_uint32),
         ("withLBHeader", C.c_int),
+        ("eventStep", C.c_uint32),    # 0 or 1: consecutive events; S > 1: position i holds event base + i * S
+        ("eventPhase", C.c_uint32),   # the window's events are those with eventNum % S == eventPhase
     ]
 
 
@@ -262,7 +264,7 @@ assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
 assert C.sizeof(BuiltRec) == 32
 assert C.sizeof(TurnMarks) == 24
-assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 56
+assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 64
 assert C.sizeof(RowsReadyRule) == 24 and C.sizeof(RowsEvent) == 32
 
 vp = C.c_void_p

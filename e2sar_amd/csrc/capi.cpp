@@ -663,6 +663,7 @@ static int check_rows(const e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, RowsDev
     if (((uintptr_t)w->d_cells & 15u) || ((uintptr_t)w->d_base & 7u) || ((uintptr_t)w->d_counts & 7u))
         return fail(E2SAR_HIP_ERR_PARAMETER, "cells must be 16-byte aligned, base and counts 8-byte aligned");
     if ((uint64_t)w->nEvents * w->nIds > 0xFFFFFFFFull) return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "more than 2^32 - 1 cells");
+    if (w->eventPhase >= std::max(w->eventStep, 1u)) return fail(E2SAR_HIP_ERR_PARAMETER, "eventPhase must be below max(eventStep, 1)");
     W = RowsDev{};
     W.out = w->d_out;
     W.cells = w->d_cells;
@@ -673,6 +674,12 @@ static int check_rows(const e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, RowsDev
     W.pitch = w->pitch;
     W.withLB = w->withLBHeader ? 1 : 0;
     std::copy(w->dataIds, w->dataIds + w->nIds, W.ids);
+    if (w->eventStep > 1u) {                                          // a lattice; otherwise step, phase and magic stay 0
+        const uint64_t S = w->eventStep, top = ~0ull;
+        W.step = w->eventStep;
+        W.phase = w->eventPhase;
+        W.magic = top / S + (top % S == S - 1u ? 1u : 0u);            // floor(2^64 / S): rows_lattice's multiplier
+    }
     return E2SAR_HIP_OK;
 }
 
@@ -688,7 +695,7 @@ int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const
     if (int rc = check_slots(W.withLB != 0, d_packets, stride, maxPackets)) return rc;
     if (maxPackets == 0) return E2SAR_HIP_OK;
     return ctx_call(ctx, stream, "rows reassembly launch", [&](hipStream_t s) -> int {
-        if (rows_grid(maxPackets, stride) > 0x7FFFFFFFull)
+        if (rows_grid(maxPackets, stride, W.step > 1u) > 0x7FFFFFFFull)
             return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "launch too large (workgroups of maxPackets)");
         const hipError_t e = launch_rows(W, d_packets, stride, d_lens, d_count, maxPackets, s);
         return e == hipSuccess ? E2SAR_HIP_OK : hip_fail(e, "rows reassembly launch");
@@ -706,6 +713,8 @@ int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t e
 {
     RowsDev W;
     if (int rc = check_rows(ctx, w, W)) return rc;
+    if (W.step > 1u && eventBase % W.step != W.phase)
+        return fail(E2SAR_HIP_ERR_PARAMETER, "eventBase mod eventStep must be eventPhase");
     return ctx_call(ctx, stream, "rows clear launch", [&](hipStream_t s) { return launch_rows_clear(W, eventBase, s); });
 }
 

@@ -15,6 +15,11 @@ namespace e2sar_amd {
 // nEvents, cell j where ids[j] == dataId, byte bufferOffset.  What is left of reas_kernel's
 // classification is one compare-and-swap per run head (the cell's length: whoever finds 0
 // opens the cell) and one add per run tail (the cell's accumulator); the copy is reas_kernel's.
+//   A window on a lattice (eventStep S > 1, the template parameter LAT) holds one rank's share of
+// such a stream, the events with eventNum mod S == eventPhase: what was said of eventNum holds of
+// the event's index eventNum / S, and a datagram of another rank's event is passed over at the
+// price of its header -- every wave learns that before it issues a payload load (rows_range).
+// LAT = false is the consecutive window: its code does not know the lattice.
 
 static_assert(sizeof(e2sar_hip_rows_cell) == 16 && offsetof(e2sar_hip_rows_cell, bytes) == 8 &&
                   offsetof(e2sar_hip_rows_cell, flags) == 12,
@@ -23,16 +28,50 @@ static_assert(sizeof(e2sar_hip_rows_cell) == 16 && offsetof(e2sar_hip_rows_cell,
 // counts[] of a window
 enum : uint32_t {
     kRowsComplete = 0, kRowsAccepted = 1, kRowsBytes = 2, kRowsLate = 3, kRowsEarly = 4, kRowsForeign = 5,
-    kRowsBadHeader = 6, kRowsDataErr = 7, kRowsReleased = 8, kRowsReleasedComplete = 9
+    kRowsBadHeader = 6, kRowsDataErr = 7, kRowsReleased = 8, kRowsReleasedComplete = 9,
+    kRowsNotOwned = 10             // a lattice only: another rank's event
 };
 
 // Per-workgroup LDS: destinations of the group's datagrams, and what the run tails need
 // after the copy (only the add's return value stays in a register meanwhile).
+template <bool LAT = false>
 struct RowsGroupLds {
     PktInfo info[64];
     uint32_t cell[64], bytes[64], rb[64], tail[64];
-    uint64_t cnt[8];               // the group's additions to counts[0..7] ([0]: known after the copy)
+    uint64_t cnt[LAT ? 9 : 8];     // the group's additions to counts[0..7] ([0]: known after the copy); [8]: to counts[10]
 };
+static_assert(sizeof(RowsGroupLds<false>) == 2112, "the consecutive window's LDS is what it was");
+
+// The lattice of a window with eventStep S > 1: the index eventNum / S of an event, and whether
+// the window owns it (eventNum mod S == eventPhase).  Exact for every 64-bit eventNum and every
+// S in [2, 2^32): with M = floor(2^64 / S) from the host (RowsDev.magic), ev * M / 2^64 lies in
+// (ev / S - 1, ev / S], so the product's high half is the quotient or one below it, and the
+// remainder -- below 2 S -- says which.  Four 32-bit multiplies and a compare: no division
+// sequence, no scratch.
+struct RowsPos {
+    uint64_t q;
+    bool owned;
+};
+__device__ __forceinline__ RowsPos rows_lattice(const RowsDev &W, uint64_t ev)
+{
+    uint64_t q = __umul64hi(ev, W.magic);
+    uint64_t r = ev - q * W.step;
+    if (r >= W.step) {
+        q++;
+        r -= W.step;
+    }
+    return RowsPos{q, r == W.phase};
+}
+// The upkeep kernels' view, the step a run-time value: the index of the window's first
+// position, and the event numbers from one position to the next
+__device__ __forceinline__ uint64_t rows_base_index(const RowsDev &W)
+{
+    const uint64_t b = *W.base;
+    return W.step > 1u ? rows_lattice(W, b).q : b;
+}
+__device__ __forceinline__ uint64_t rows_stride(const RowsDev &W) { return W.step > 1u ? W.step : 1u; }
+// eventNum of a raw header, as parse_hdr reads it
+__device__ __forceinline__ uint64_t raw_event(const RawHdr &raw) { return ((uint64_t)bswap32(raw.re.w) << 32) | bswap32(raw.re4); }
 
 // The number of lanes of a whole wave for which `on` holds, added to counts[k] by the wave's
 // lane 0 -- no atomic when there is none.
@@ -46,14 +85,24 @@ __device__ __forceinline__ void rows_count(uint64_t *counts, uint32_t k, bool on
 // below gn): the rules of e2sar_hip_rows_reassemble in their order.  Leaves every
 // datagram's destination in L.info, the run tails' state and the group's counts in L; returns
 // the value the tail's accumulator add found (consumed after the copy, rows_finish).
+template <bool LAT>
 __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, const RawHdr &raw, uint32_t stride,
-                                                            bool live, RowsGroupLds &L)
+                                                            bool live, RowsGroupLds<LAT> &L)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
     const ParsedHdr h = parse_hdr(raw, hl, stride, live);
     bool ok = h.ok, derr = h.derr;
 
+    // a lattice: the event's index stands where its number stood; another rank's event stops here
+    uint64_t idx = h.ev;
+    bool notOwned = false;
+    if constexpr (LAT) {
+        const RowsPos p = rows_lattice(W, h.ev);
+        idx = p.q;
+        notOwned = ok && !p.owned;
+        ok = ok && p.owned;
+    }
     // the cell's column: the place of the dataId among the window's ids
     uint32_t j = ~0u;
     for (uint32_t k = 0; k < W.nIds; k++)
@@ -61,7 +110,8 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
     const bool foreign = ok && j == ~0u;
     ok = ok && !foreign;
     // the window, by 64-bit wrap-around distance from its base
-    const uint64_t dist = h.ev - *W.base;
+    uint64_t dist = h.ev - *W.base;
+    if constexpr (LAT) dist = idx - rows_lattice(W, *W.base).q;
     const bool outside = ok && dist >= (uint64_t)W.nEvents;
     const bool late = outside && (int64_t)dist < 0;
     ok = ok && !outside;
@@ -70,7 +120,7 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
         ok = false;
         derr = true;
     }
-    const uint32_t cell = ok ? ((uint32_t)h.ev & (W.nEvents - 1u)) * W.nIds + j : ~0u;
+    const uint32_t cell = ok ? ((uint32_t)idx & (W.nEvents - 1u)) * W.nIds + j : ~0u;
 
     // ---- runs of one cell: consecutive lanes of one (eventNum, dataId) inside the window ----
     const uint32_t pc = lane_prev(cell, ~0u), nc = lane_next(cell, ~0u);
@@ -128,17 +178,20 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
                         ((uint64_t)readlane(wave_incl_scan(tl >> 16), 63) << 16);
     const uint64_t votes[8] = {0ull, __ballot(take), 0ull, __ballot(late), __ballot(outside && !late), __ballot(foreign),
                                __ballot(h.bad), __ballot(derr)};
+    const uint64_t voteNotOwned = LAT ? __ballot(notOwned) : 0ull;
     if (lane == 0u) {
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) L.cnt[k] = (uint64_t)__builtin_popcountll(votes[k]);
         L.cnt[kRowsBytes] = tb;
+        if constexpr (LAT) L.cnt[8] = (uint64_t)__builtin_popcountll(voteNotOwned);
     }
     return old;
 }
 
 // After the copy, by the classifying wave: a tail whose add of more than 0 bytes brought the
 // cell's curBytes to its length marks the cell complete.
-__device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long old, const RowsGroupLds &L)
+template <bool LAT>
+__device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long old, const RowsGroupLds<LAT> &L)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t rb = L.rb[lane];
@@ -146,7 +199,12 @@ __device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long
     if (done) atomicOr(&W.cells[L.cell[lane]].flags, E2SAR_HIP_ROWS_COMPLETE);
     // the workgroup's counts: lane k adds to counts[k], one instruction for all eight
     const uint64_t ndone = (uint64_t)__builtin_popcountll(__ballot(done));
-    if (lane < 8u) {
+    if constexpr (LAT) {                                               // lane 8: counts[10]
+        if (lane < 9u) {
+            const uint64_t v = (lane == kRowsComplete) ? ndone : L.cnt[lane];
+            if (v) atomicAdd((unsigned long long *)(W.counts + (lane < 8u ? lane : kRowsNotOwned)), (unsigned long long)v);
+        }
+    } else if (lane < 8u) {
         const uint64_t v = (lane == kRowsComplete) ? ndone : L.cnt[lane];
         if (v) atomicAdd((unsigned long long *)(W.counts + lane), (unsigned long long)v);
     }
@@ -154,16 +212,17 @@ __device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long
 
 // One group of gn <= 64 consecutive datagrams [g0, g0 + gn), by the whole workgroup -- the
 // steps of reas_range (reas_fused.hpp) around the same group_copy (reas_copy.hpp):
-//   1. every wave loads the group's headers (lane p: datagram p);
+//   1. every wave loads the group's headers (lane p: datagram p); on a lattice every wave then
+//      finds the datagrams of other ranks' events and loads no payload for them;
 //   2. every thread issues its first U destination-aligned 16-byte payload loads -- the
 //      phase is bufferOffset mod 16: cells are 256-byte aligned;
 //   3. wave 0 classifies (rows_classify) while those loads are in flight;
 //   4. every thread stores its chunks (da_store), then loads and stores the rest round by
 //      round, the loads of round r + 1 issued before the stores of round r;
 //   5. wave 0's run tails mark completed cells (rows_finish).
-template <int U, int NT>
+template <int U, int NT, bool LAT>
 __device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__restrict__ pkts, uint32_t stride,
-                                           const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn, RowsGroupLds &L)
+                                           const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn, RowsGroupLds<LAT> &L)
 {
     const bool w0 = threadIdx.x < 64;
     const uint32_t lane = threadIdx.x & 63u;
@@ -171,33 +230,39 @@ __device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__re
     const RawHdr raw = load_hdr(W.withLB != 0, pkts, stride, lens, g0 + ((lane < gn) ? lane : 0u));
     const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
 
-    unsigned long long old = 0;
-    group_copy<U, false, NT>(pkts, stride, g0, gn, hl, bswap32(raw.re.y) & kPhaseMask,
-                             hdr_payload_len(raw.len, hl, stride), L.info,
-                             [&] { if (w0) old = rows_classify(W, raw, stride, lane < gn, L); });
+    // Whatever else its header says, a datagram whose event number is not the window's is not
+    // taken (rule 1 or 1b): payload length 0, as reas_range has it for a foreign event.
+    uint32_t gPlen = hdr_payload_len(raw.len, hl, stride);
+    if constexpr (LAT)
+        if (!rows_lattice(W, raw_event(raw)).owned) gPlen = 0u;
 
-    if (w0) rows_finish(W, old, L);
+    unsigned long long old = 0;
+    group_copy<U, false, NT>(pkts, stride, g0, gn, hl, bswap32(raw.re.y) & kPhaseMask, gPlen, L.info,
+                             [&] { if (w0) old = rows_classify<LAT>(W, raw, stride, lane < gn, L); });
+
+    if (w0) rows_finish<LAT>(W, old, L);
 }
 
 // rows_kernel: workgroup b takes datagrams [b*G, b*G + G) of the first n = min(*count,
 // bound) (count NULL: bound); the grid is cdiv(bound, G).  A workgroup at or past n costs the
 // load of one word and an exit (reas_devcount.hpp): no header load, no LDS, no counter.
-template <int U, int NT>
+// LAT: the window is on a lattice (RowsDev.step > 1).
+template <int U, int NT, bool LAT = false>
 __global__ __launch_bounds__(NT) void rows_kernel(RowsDev W, const uint8_t *__restrict__ pkts, uint32_t stride,
                                                   const uint32_t *__restrict__ lens, const uint32_t *__restrict__ count,
                                                   uint32_t bound, uint32_t G)
 {
-    __shared__ RowsGroupLds L;
+    __shared__ RowsGroupLds<LAT> L;
     const uint32_t n = count ? dev_count(count, bound) : bound;
     const uint64_t g0 = (uint64_t)blockIdx.x * G;
     if (g0 >= n) return;
-    rows_range<U, NT>(W, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);
+    rows_range<U, NT, LAT>(W, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);
 }
 
 // ---------------------------------------------------------------------------------
 // the ring's upkeep
 
-// k = min(*d_k, kMax, nEvents): the events the window lets go of
+// k = min(*d_k, kMax, nEvents): the positions the window lets go of
 __device__ __forceinline__ uint32_t rows_advance_k(const RowsDev &W, const uint32_t *__restrict__ d_k, uint32_t kMax)
 {
     uint32_t k = kMax < W.nEvents ? kMax : W.nEvents;
@@ -208,7 +273,7 @@ __device__ __forceinline__ uint32_t rows_advance_k(const RowsDev &W, const uint3
     return k;
 }
 
-// Thread t < k * nIds: the cell of event base + t / nIds, source t % nIds, is counted
+// Thread t < k * nIds: the cell of position t / nIds behind the base, source t % nIds, is counted
 // (released incomplete, released complete) and zeroed.  The base moves in a launch of its
 // own, after every workgroup here has read it.  Grid: cdiv(min(kMax, nEvents) * nIds, kBlock).
 __global__ __launch_bounds__(kBlock) void rows_release_kernel(RowsDev W, const uint32_t *__restrict__ d_k, uint32_t kMax)
@@ -219,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void rows_release_kernel(RowsDev W, const u
     bool open = false, complete = false;
     if (in) {
         const uint64_t e = t / W.nIds;
-        const uint64_t c = ((*W.base + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + (t - e * W.nIds);
+        const uint64_t c = ((rows_base_index(W) + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + (t - e * W.nIds);
         uint8_t *cp = reinterpret_cast<uint8_t *>(W.cells + c);
         const u32x4 v = ld16(cp);
         complete = (v.w & E2SAR_HIP_ROWS_COMPLETE) != 0u;
@@ -232,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void rows_release_kernel(RowsDev W, const u
 
 __global__ __launch_bounds__(64) void rows_shift_kernel(RowsDev W, const uint32_t *__restrict__ d_k, uint32_t kMax)
 {
-    if (threadIdx.x == 0) *W.base += rows_advance_k(W, d_k, kMax);
+    if (threadIdx.x == 0) *W.base += rows_advance_k(W, d_k, kMax) * rows_stride(W);
 }
 
 // Every cell and all 16 counts zeroed, the base set: stores only, so it can be captured

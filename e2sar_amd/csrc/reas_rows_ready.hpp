@@ -31,14 +31,14 @@ __device__ __forceinline__ uint8_t *rows_trunc(void *work, uint32_t nEvents, uin
     return static_cast<uint8_t *>(work) + 16ull * nEvents + 4ull * i;
 }
 
-// Thread i < nEvents: the cells of event base + i, nIds 16-byte loads, as two masks and a word.
+// Thread i < nEvents: the cells of position i (event base + i * step), nIds 16-byte loads, as two masks and a word.
 // Grid: cdiv(nEvents, kBlock).
 __global__ __launch_bounds__(kBlock) void rows_scan_kernel(RowsDev W, void *work)
 {
     const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= W.nEvents) return;
     const uint32_t i = (uint32_t)t;
-    const uint64_t c0 = ((*W.base + i) & (uint64_t)(W.nEvents - 1u)) * W.nIds;
+    const uint64_t c0 = ((rows_base_index(W) + i) & (uint64_t)(W.nEvents - 1u)) * W.nIds;
     uint64_t present = 0, open = 0;
     uint32_t trunc = 0;
     for (uint32_t j = 0; j < W.nIds; j++) {
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void rows_ready_kernel(RowsDev W, RowsRule 
         }
     }
 
-    const uint64_t base = *W.base;
+    const uint64_t base = *W.base, qb = rows_base_index(W), step = rows_stride(W);
     uint32_t nComplete = 0, nGivenUp = 0, cellsComplete = 0, cellsOpen = 0;
     for (uint32_t i = threadIdx.x; i < k; i += kBlock) {
         const RowsSummary s = rows_summary_of(work, i);
@@ -127,10 +127,10 @@ __global__ __launch_bounds__(kBlock) void rows_ready_kernel(RowsDev W, RowsRule 
         cellsOpen += (uint32_t)__builtin_popcountll(s.open & ~s.present);
         if (events) {
             e2sar_hip_rows_event ev;
-            ev.eventNum = base + i;
+            ev.eventNum = base + i * step;
             ev.presentMask = s.present;
             ev.openMask = s.open;
-            ev.row = (uint32_t)(ev.eventNum & (uint64_t)(N - 1u));
+            ev.row = (uint32_t)((qb + i) & (uint64_t)(N - 1u));
             ev.flags = (complete ? E2SAR_HIP_ROWS_EV_COMPLETE : E2SAR_HIP_ROWS_EV_GIVEN_UP) |
                        (ld4(rows_trunc(work, N, i)) ? E2SAR_HIP_ROWS_EV_TRUNCATED : 0u);
             events[i] = ev;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void rows_ready_kernel(RowsDev W, RowsRule 
 }
 
 // Workgroup p: piece p % perCell (kCopyPiece bytes, copy_piece's) of cell (p / perCell) % nIds
-// of event base + (p / perCell) / nIds.  Past k = ready[0]: one load and out.  A piece wholly
+// of position (p / perCell) / nIds behind the base.  Past k = ready[0]: one load and out.  A piece wholly
 // inside the first min(bytes, pitch) bytes of a COMPLETE cell: two loads and out -- every
 // workgroup of a loss-free batch of pitch-long events.  Otherwise zeros from the end of the
 // event's bytes (from 0 where the cell is not COMPLETE) to the end of the piece: 16-byte
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void rows_zero_kernel(RowsDev W, const uint
     const uint32_t e = c / W.nIds;
     if (e >= ready[0]) return;
     const uint32_t j = c - e * W.nIds;
-    const uint64_t cell = ((*W.base + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + j;
+    const uint64_t cell = ((rows_base_index(W) + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + j;
     const u32x4 v = ld16(reinterpret_cast<const uint8_t *>(W.cells + cell));
     const uint32_t keep = (v.w & E2SAR_HIP_ROWS_COMPLETE) ? (v.z < W.pitch ? v.z : W.pitch) : 0u;
     const uint32_t pb = (blockIdx.x - c * perCell) * kCopyPiece;

@@ -459,19 +459,21 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
 
 // The launch's geometry for a bound of maxPackets: G datagrams per workgroup -- reas_kernel's
 // rule (reas_group_size), balanced over this kernel's residency; returns the grid.
-static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, uint32_t &G)
+// lattice: the window's eventStep is above 1, and the kernel is the instantiation that knows it.
+static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, bool lattice, uint32_t &G)
 {
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        G = reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT>, NT>);
+        G = lattice ? reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT, true>, NT>)
+                    : reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT>, NT>);
     });
     return ((uint64_t)maxPackets + G - 1u) / G;
 }
 
-uint64_t rows_grid(uint32_t maxPackets, uint32_t stride)
+uint64_t rows_grid(uint32_t maxPackets, uint32_t stride, bool lattice)
 {
     uint32_t G = 1;
-    return rows_geometry(maxPackets, stride, G);
+    return rows_geometry(maxPackets, stride, lattice, G);
 }
 
 hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
@@ -480,12 +482,17 @@ hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, c
     constexpr int U = kReasU;
     if (maxPackets == 0) return hipSuccess;
     uint32_t G = 1;
-    const uint64_t grid = rows_geometry(maxPackets, stride, G);
+    const bool lattice = W.step > 1u;
+    const uint64_t grid = rows_geometry(maxPackets, stride, lattice, G);
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        hipLaunchKernelGGL((rows_kernel<U, NT>), dim3((uint32_t)grid), dim3(NT), reas_lds<NT>(rows_kernel<U, NT>), stream, W,
-                           pkts, stride, lens, d_count, maxPackets, G);
+        if (lattice)
+            hipLaunchKernelGGL((rows_kernel<U, NT, true>), dim3((uint32_t)grid), dim3(NT),
+                               reas_lds<NT>(rows_kernel<U, NT, true>), stream, W, pkts, stride, lens, d_count, maxPackets, G);
+        else
+            hipLaunchKernelGGL((rows_kernel<U, NT>), dim3((uint32_t)grid), dim3(NT), reas_lds<NT>(rows_kernel<U, NT>), stream, W,
+                               pkts, stride, lens, d_count, maxPackets, G);
     });
     return hipGetLastError();
 }

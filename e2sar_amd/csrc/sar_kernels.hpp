@@ -320,11 +320,17 @@ struct RowsDev {
     uint32_t nIds, nEvents, pitch;
     int withLB;
     uint16_t ids[E2SAR_HIP_ROWS_MAX_IDS];
+    // The lattice (eventStep S > 1; behind the ids, so that a consecutive window's kernels read
+    // what they always read): position i holds event *base + i * S, *base mod S == phase;
+    // magic = floor(2^64 / S), the host's multiplier for eventNum / S (rows_lattice).  step <= 1:
+    // a consecutive window, phase and magic 0.
+    uint64_t magic;
+    uint32_t step, phase;
 };
 // rows_kernel over n = min(*d_count, maxPackets) datagrams (d_count NULL: maxPackets): its
 // grid, from maxPackets and the stride alone (above 2^31 - 1: no launch is possible), and the
-// one launch
-uint64_t rows_grid(uint32_t maxPackets, uint32_t stride);
+// one launch; lattice: W.step > 1 (another instantiation, its own residency)
+uint64_t rows_grid(uint32_t maxPackets, uint32_t stride, bool lattice);
 hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
                        const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream);
 // rows_release_kernel, then rows_shift_kernel; and rows_clear_kernel

@@ -666,13 +666,22 @@ class RowWindow:
     holds.  alloc_ready() and ready() add the delivery half: which of the oldest events are whole or
     given up is decided on the device, their rows are zero-filled on request, and the count goes
     to advance() as a device word.
+
+    With step = S > 1 and phase = P the window is one rank's share of a stream sharded by
+    eventNum % S (dist.owner): position i holds event base + i * S, base % S == P, the row of an
+    event is (eventNum // S) mod n_events, and a datagram of another rank's event is passed over
+    at the price of its header and counted in counts[10].  advance(), ready()'s slack and k_max
+    then count positions, that is owned events.  Event numbers do not wrap on such a window.
     """
 
     def __init__(self, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, event_base: int = 0,
-                 with_lb_header: bool = True):
+                 with_lb_header: bool = True, step: int = 1, phase: int = 0):
         ids = [int(d) for d in ids]
         if not ids or len(ids) > _capi.ROWS_MAX_IDS:
             raise ValueError("a RowWindow names 1..64 dataIds")
+        self.step, self.phase = int(step), int(phase)
+        if self.step > 1 and (int(event_base) & 0xFFFFFFFFFFFFFFFF) % self.step != self.phase:
+            raise ValueError("event_base % step must be phase")
         self.ctx = ctx
         self.ids = ids
         self.n_events = int(n_events)
@@ -685,8 +694,25 @@ class RowWindow:
         self.counts = torch.empty(16, dtype=torch.int64, device=dev)
         self._ids = (C.c_uint16 * len(ids))(*ids)
         self._w = _capi.Rows(self.out.data_ptr(), self.cells.data_ptr(), self.base.data_ptr(), self.counts.data_ptr(),
-                             self._ids, len(ids), self.n_events, self.pitch, 1 if with_lb_header else 0)
+                             self._ids, len(ids), self.n_events, self.pitch, 1 if with_lb_header else 0, self.step, self.phase)
         self.clear(event_base)
+
+    @staticmethod
+    def first_owned(first_event: int, world: int, rank: int) -> int:
+        """The smallest event number >= first_event that rank `rank` of `world` owns
+        (eventNum % world == rank)."""
+        first_event, world, rank = int(first_event), int(world), int(rank)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("rank must be in [0, world)")
+        return first_event + (rank - first_event) % world
+
+    @classmethod
+    def for_rank(cls, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, world: int, rank: int,
+                 first_event: int = 0, with_lb_header: bool = True) -> "RowWindow":
+        """The window of rank `rank` of `world` on a stream that starts at first_event: step world,
+        phase rank, its base the rank's first event (first_owned)."""
+        return cls(ctx, ids, n_events, pitch, cls.first_owned(first_event, world, rank), with_lb_header,
+                   step=world, phase=rank)
 
     def reassemble(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, max_packets: int,
                    count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
@@ -702,7 +728,7 @@ class RowWindow:
               _p(count), max_packets, _s(stream))
 
     def advance(self, k: int, count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """Let go of the min(count[0], k, n_events) oldest events -- min(k, n_events) when
+        """Let go of the min(count[0], k, n_events) oldest events (positions of the window) -- min(k, n_events) when
         `count` (int32 device tensor) is omitted: their cells are counted (counts[8] released
         incomplete, counts[9] complete) and zeroed, and the base moves on
         (e2sar_hip_rows_advance).  No host read, capturable."""
@@ -712,7 +738,7 @@ class RowWindow:
 
     def clear(self, event_base: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Every cell and count zeroed, the window at [event_base, event_base + n_events)
-        (e2sar_hip_rows_clear); row bytes stay."""
+        (e2sar_hip_rows_clear; on a lattice event_base % step must be phase); row bytes stay."""
         _call("e2sar_hip_rows_clear", self.ctx.handle, C.byref(self._w), int(event_base) & 0xFFFFFFFFFFFFFFFF, _s(stream))
 
     def alloc_ready(self, k_max: int) -> None:

@@ -681,7 +681,21 @@ int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src,
 /*   d_counts (device u64[16], accumulating): [0] cells completed, [1] fragments          */
 /* accepted, [2] their payload bytes, [3] late (behind the window), [4] early (ahead of   */
 /* it), [5] foreign dataId, [6] bad header, [7] data error, [8] cells released incomplete */
-/* by advance, [9] cells released complete; [10..15] reserved, written only by clear.     */
+/* by advance, [9] cells released complete, [10] datagrams of events the window does not   */
+/* own (a lattice only, below); [11..15] reserved, written only by clear.                 */
+/*   The lattice.  Events are sharded over W consumers by eventNum mod W (the multi-GPU    */
+/* section below); the window of consumer r holds its share, not every event number.      */
+/* With eventStep = S > 1 and eventPhase = P < S, position i of the window holds event    */
+/* *d_base + i * S, where *d_base mod S == P.  Let q(ev) = ev / S (floor) and owned(ev)   */
+/* <=> ev mod S == P: wherever this family says eventNum of a row, a distance or the      */
+/* window's extent, read q(eventNum) -- the row of an owned event is q(ev) & (nEvents -   */
+/* 1), its distance from the base q(ev) - q(*d_base), and the window holds the nEvents    */
+/* owned events from *d_base on.  *d_base itself stays an event number.  kMax, slack, k   */
+/* and the horizon H of the calls below count window positions, that is owned events,     */
+/* not raw event numbers.  q is exact for every 64-bit eventNum and every S < 2^32.       */
+/* Event numbers do not wrap on a lattice: a stream is assumed to stay below 2^64 -       */
+/* nEvents * S.  eventStep 0 or 1 is the consecutive window, bit for bit, with its 64-bit */
+/* wrap; eventPhase must then be 0.                                                       */
 #define E2SAR_HIP_ROWS_MAX_IDS 64u
 #define E2SAR_HIP_ROWS_COMPLETE 1u
 #define E2SAR_HIP_ROWS_TRUNCATED 2u
@@ -701,7 +715,9 @@ typedef struct e2sar_hip_rows {
     uint32_t nEvents;             /* power of two */
     uint32_t pitch;               /* multiple of 256 */
     int withLBHeader;
-} e2sar_hip_rows;
+    uint32_t eventStep;           /* 0 or 1: consecutive events; S > 1: position i holds event base + i * S */
+    uint32_t eventPhase;          /* < max(eventStep, 1): the window's events have eventNum mod S == eventPhase */
+} e2sar_hip_rows;                 /* 64 bytes */
 
 /* The datagrams [0, n) of a batch into the window, n = min(*d_count, maxPackets), or     */
 /* maxPackets when d_count is NULL.  Slots and lengths: e2sar_hip_reassemble_batch's      */
@@ -712,9 +728,12 @@ typedef struct e2sar_hip_rows {
 /*   1. header: the validation of e2sar_hip_reassemble_batch (cpp:340-357): a bad RE      */
 /*      version or a datagram too short for its headers -> counts[6]; a datagram longer   */
 /*      than its slot -> counts[7];                                                       */
+/*   1b. (eventStep > 1) an event the window does not own, eventNum mod S != P ->        */
+/*      counts[10]; such a datagram costs its header read only: no wave loads its payload;*/
 /*   2. a dataId that is not in dataIds -> counts[5];                                     */
-/*   3. window: d = eventNum - *d_base (64-bit wrap); d >= nEvents -> counts[3] (late)    */
-/*      when (int64_t)d < 0, else counts[4] (early);                                      */
+/*   3. window: d = eventNum - *d_base (64-bit wrap; on a lattice q(eventNum) -           */
+/*      q(*d_base)); d >= nEvents -> counts[3] (late) when (int64_t)d < 0, else counts[4] */
+/*      (early);                                                                          */
 /*   4. own bounds: bufferLength == 0, or bufferOffset + payload > bufferLength (64 bits) */
 /*      -> counts[7]; such a fragment opens no cell;                                      */
 /*   5. the cell's length S is its `bytes` if that is not 0; otherwise this fragment      */
@@ -726,7 +745,8 @@ typedef struct e2sar_hip_rows {
 /*      was cut; counts[1] += 1, counts[2] += payload; an add of more than 0 bytes that   */
 /*      brings curBytes to exactly S sets COMPLETE and adds 1 to counts[0].               */
 /* A datagram stopped by rules 1-5 writes nothing and touches no cell.  Never written:    */
-/* bytes of d_out outside the accepted fragments' (cut) extents, counts[8..15].           */
+/* bytes of d_out outside the accepted fragments' (cut) extents, counts[8..9] and         */
+/* counts[11..15], and counts[10] by a consecutive window.                                */
 /*   Consecutive datagrams of one cell may be added as one.  The result does not depend   */
 /* on the order of the datagrams nor on how a stream is cut into batches, provided no     */
 /* fragment arrives twice and each cell has one determinate opener within a launch (all   */
@@ -737,28 +757,30 @@ typedef struct e2sar_hip_rows {
 /* Status: PARAMETER for a NULL ctx, w, d_packets or d_lens, a NULL d_out, d_cells,       */
 /* d_base, d_counts or dataIds, nIds 0 or above 64 or a repeated id, nEvents 0 or not a   */
 /* power of two, pitch 0 or not a multiple of 256, d_out not 256-byte aligned, d_cells    */
-/* not 16-byte or d_base / d_counts not 8-byte aligned, a stride or packet pointer        */
-/* e2sar_hip_reassemble_batch refuses; OUT_OF_RANGE when nEvents * nIds exceeds 2^32 - 1, */
-/* maxPackets * (stride / 16) exceeds 2^32 - 1 or the launch would exceed 2^31 - 1        */
-/* workgroups.  maxPackets == 0 succeeds with nothing launched; a failing call launches   */
-/* nothing.  Asynchronous.                                                                */
+/* not 16-byte or d_base / d_counts not 8-byte aligned, eventPhase >= max(eventStep, 1),  */
+/* a stride or packet pointer e2sar_hip_reassemble_batch refuses; OUT_OF_RANGE when       */
+/* nEvents * nIds exceeds 2^32 - 1, maxPackets * (stride / 16) exceeds 2^32 - 1 or the    */
+/* launch would exceed 2^31 - 1 workgroups.  maxPackets == 0 succeeds with nothing        */
+/* launched; a failing call launches nothing.  Asynchronous.                              */
 int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint8_t *d_packets,
                               uint32_t stride, const uint32_t *d_lens, const uint32_t *d_count,
                               uint32_t maxPackets, void *stream);
 
 /* The ring's upkeep, decided on the device: k = min(*d_k, kMax, nEvents), or min(kMax,   */
-/* nEvents) when d_k is NULL.  For each of the k oldest events, base .. base + k - 1, and */
+/* nEvents) when d_k is NULL.  For each of the k oldest events, base .. base + k - 1 (on a */
+/* lattice the k oldest positions, base, base + S, .. base + (k - 1) * S), and            */
 /* every id: a cell with bytes != 0 and no COMPLETE adds 1 to counts[8] -- the loss a     */
 /* garbage-collection pass of the reference would log (cpp:283-308) -- a COMPLETE cell    */
 /* adds 1 to counts[9], and the cell is zeroed; row bytes are not touched.  Then *d_base  */
-/* += k (64-bit wrap).  k == 0 changes nothing.  Two launches, their grids from nEvents * */
+/* += k (64-bit wrap; on a lattice k * S).  k == 0 changes nothing.  Two launches, their grids from nEvents * */
 /* nIds and kMax alone; capturable as above.  Status: PARAMETER as above (ctx, w and the  */
 /* descriptor).  Asynchronous.                                                            */
 int e2sar_hip_rows_advance(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint32_t *d_k,
                            uint32_t kMax, void *stream);
 
 /* Every cell and all 16 counts zeroed, *d_base = eventBase; row bytes are not touched.   */
-/* One launch of plain stores (no memset node), capturable.  Status as above.             */
+/* One launch of plain stores (no memset node), capturable.  Status as above, and         */
+/* PARAMETER for an eventBase with eventBase mod eventStep != eventPhase (eventStep > 1). */
 int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t eventBase, void *stream);
 
 /* Which events are ready, decided on the device: the k that e2sar_hip_rows_advance takes,    */
@@ -769,7 +791,8 @@ int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t e
 /* the clock is distance in event numbers, not time, for the reason e2sar_hip_reas_turn      */
 /* gives for its carry count -- a now_ms is frozen in a replayed graph.                      */
 /*   Let N = nEvents, B = *d_base and i in [0, N): event i is B + i (64-bit wrap), its row   */
-/* (B + i) & (N - 1); open(i) are the ids whose cell has bytes != 0, present(i) those whose  */
+/* (B + i) & (N - 1) -- on a lattice event i is B + i * S and its row (q(B) + i) & (N - 1),  */
+/* and i, H, slack, kMax and k all count positions of the window, that is owned events; open(i) are the ids whose cell has bytes != 0, present(i) those whose  */
 /* cell is COMPLETE; R = requiredMask, or all nIds bits when that is 0.  The horizon H is 0  */
 /* when no cell of the window is open, else 1 + the largest i with an open cell.  Per event, */
 /* the first rule that applies:                                                              */
@@ -783,7 +806,7 @@ int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t e
 /* that are COMPLETE, over all ids and not only R; [5] their cells that are open and not     */
 /* COMPLETE; [6], [7] 0.                                                                     */
 /*   d_events (device, min(kMax, N) records, or NULL: only the counts are written):          */
-/* d_events[i], i < k, describes event B + i, in event order; `flags` has COMPLETE or        */
+/* d_events[i], i < k, describes event B + i (B + i * S), in event order; `flags` has COMPLETE or        */
 /* GIVEN_UP, and TRUNCATED when a cell of the event has E2SAR_HIP_ROWS_TRUNCATED.  The       */
 /* event's cells start at row * nIds, its bytes at d_out + row * nIds * pitch.               */
 /*   With E2SAR_HIP_ROWS_READY_ZERO, for every i < k and every j < nIds, required or not: a  */
@@ -823,7 +846,7 @@ typedef struct e2sar_hip_rows_event {   /* 32 bytes */
     uint64_t eventNum;
     uint64_t presentMask;  /* bit j: cell (event, dataIds[j]) is COMPLETE */
     uint64_t openMask;     /* bit j: cell's bytes != 0 */
-    uint32_t row;          /* eventNum & (nEvents - 1): its cells start at row * nIds */
+    uint32_t row;          /* eventNum & (nEvents - 1), on a lattice q(eventNum) & (nEvents - 1): its cells start at row * nIds */
     uint32_t flags;
 } e2sar_hip_rows_event;
 

@@ -62,6 +62,10 @@ int main()
     with([](e2sar_hip_rows &w) { w.pitch = 128; });
     with([](e2sar_hip_rows &w) { w.d_out += 128; });
     with([](e2sar_hip_rows &w) { w.d_cells = reinterpret_cast<e2sar_hip_rows_cell *>(reinterpret_cast<uint8_t *>(w.d_cells) + 8); });
+    with([](e2sar_hip_rows &w) { w.eventStep = 2; w.eventPhase = 2; });        // the lattice: phase < max(step, 1)
+    with([](e2sar_hip_rows &w) { w.eventStep = 0; w.eventPhase = 1; });
+    with([](e2sar_hip_rows &w) { w.eventStep = 1; w.eventPhase = 1; });
+    with([](e2sar_hip_rows &w) { w.eventStep = 0xFFFFFFFFu; w.eventPhase = 0xFFFFFFFFu; });
     for (const e2sar_hip_rows &w : bad) {
         expect(e2sar_hip_rows_reassemble(ctx, &w, pk, 64, ln, nullptr, 4, nullptr), P, "reassemble, bad descriptor");
         expect(e2sar_hip_rows_advance(ctx, &w, nullptr, 1, nullptr), P, "advance, bad descriptor");
@@ -85,6 +89,12 @@ int main()
     expect(e2sar_hip_rows_advance(ctx, nullptr, nullptr, 1, nullptr), P, "advance, NULL descriptor");
     expect(e2sar_hip_rows_clear(nullptr, &good, 0, nullptr), P, "clear, NULL ctx");
     expect(e2sar_hip_rows_clear(ctx, nullptr, 0, nullptr), P, "clear, NULL descriptor");
+    e2sar_hip_rows third = good;
+    third.eventStep = 3;
+    third.eventPhase = 2;
+    expect(e2sar_hip_rows_clear(ctx, &third, 3, nullptr), P, "clear, eventBase off the lattice");
+    expect(e2sar_hip_rows_clear(ctx, &third, ~0ull, nullptr), P, "clear, 2^64 - 1 is 0 mod 3");
+    expect(e2sar_hip_rows_reassemble(ctx, &third, pk, 64, ln, nullptr, 0, nullptr), E2SAR_HIP_OK, "a lattice, maxPackets 0");
     std::printf("%s: %d failing\n", g_bad ? "FAILED" : "ok", g_bad);
     return g_bad ? 1 : 0;
 }

@@ -12,9 +12,19 @@ datagrams are timed with HIP events, alternating in one process after a warm-up
                      way of the arena
   reas               forced recycle outside the clock, then e2sar_hip_reassemble_batch alone
 
+With --step W[,W...] the window of rank 0 of W (eventStep W, eventPhase 0) is
+timed beside `rows` instead of the two arena forms, one form per W:
+
+  --landing own      rows_stepW: the batch holds only this rank's events, the same bytes numbered
+                     base + k W; the window takes all of them
+  --landing spread   rows_spreadW: the batch is the one `rows` takes, all W ranks' events numbered
+                     consecutively; the window takes every W-th event and passes the rest over.
+                     Reported with the time of `rows` and that time divided by W beside it.
+
 Every form's output is compared with the events' source bytes once.
 
   python tools/rows_bench.py [--events 205] [--event-bytes 1048576] [--mtus 1500,9000]
+                             [--step W[,W...]] [--landing own|spread]
                              [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).  Rates count payload bytes read + written once.
 """
@@ -91,19 +101,68 @@ def batch(ctx, args, mtu, src, torch, sar):
         ev = arena[r.arenaOffset: r.arenaOffset + B].cpu().numpy()
         assert r.bytes == B and np.array_equal(ev, host[r.eventNum - base]), ("reas", r.eventNum)
 
-    us = ab_method.measure(forms, args)
     moved = {name: 2 * E * B for name in forms}
     moved["reas+collect_rows"] = 4 * E * B
+    if args.step:
+        forms = {"rows": forms["rows"]}
+        for W in args.step:
+            name, form, owned = lattice(ctx, args, W, seg, src, host, (pk, ln, n), base, pitch, sar)
+            forms[name] = form
+            moved[name] = 2 * owned * B
+    us = ab_method.measure(forms, args)
     out = ab_method.summary(us, moved)
     out["datagrams"] = n
+    if args.step and args.landing == "spread":
+        for W in args.step:
+            out[f"rows_spread{W}"]["rows_median_over_W_us"] = round(out["rows"]["median_us"] / W, 2)
+            out[f"rows_spread{W}"]["of_rows_median"] = round(out[f"rows_spread{W}"]["median_us"] / out["rows"]["median_us"], 3)
     R.close()
     return out
+
+
+def lattice(ctx, args, W, seg, src, host, whole, base, pitch, sar):
+    """The window of rank 0 of W and the batch it is fed: -> (form name, (fn, before), owned events)."""
+    E, B = args.events, args.event_bytes
+    first = sar.RowWindow.first_owned(base, W, 0)
+    if args.landing == "own":                                      # the same bytes, numbered first + k W
+        nums = [first + i * W for i in range(E)]
+        plan = seg.plan([(src[i].data_ptr(), B, nums[i], 4321, 1 + i, nums[i]) for i in range(E)])
+        n = plan.total_packets
+        pk, ln = seg.alloc_packets(n)
+        seg.segment(plan, pk, ln)
+        owned = list(range(E))
+    else:                                                          # the whole batch: events base + i of every rank
+        pk, ln, n = whole
+        nums = [base + i for i in range(E)]
+        owned = [i for i in range(E) if nums[i] % W == 0]
+    n_events = 1
+    while n_events < len(owned):
+        n_events <<= 1
+    win = sar.RowWindow(ctx, [4321], n_events, pitch, first, with_lb_header=True, step=W, phase=0)
+    form = (lambda: win.reassemble(pk, seg.stride, ln, n), lambda: win.clear(first))
+
+    win.out.zero_()
+    form[0]()
+    c, b = win.parse_counts()
+    cells = win.parse_cells()[:, 0]
+    assert b == first and c[0] == len(owned) and c[2] == len(owned) * B and c[1] + c[10] == n and not any(c[3:10]), c
+    got = win.out[:, 0, :B].cpu().numpy()
+    for i in owned:
+        r = (nums[i] // W) & (n_events - 1)
+        assert cells[r]["flags"] == 1 and cells[r]["bytes"] == B, (W, i, cells[r])
+        assert np.array_equal(got[r], host[i]), (f"step {W}", i)
+    return ("rows_step%d" if args.landing == "own" else "rows_spread%d") % W, form, len(owned)
 
 
 def main():
     ap = ab_method.parser()
     ap.add_argument("--mtus", default="1500,9000")
+    ap.add_argument("--step", default="", help="W[,W...]: time the window of rank 0 of W beside `rows`")
+    ap.add_argument("--landing", choices=["own", "spread"], default="own")
     args = ap.parse_args()
+    args.step = [int(w) for w in args.step.split(",") if w]
+    if any(w < 2 for w in args.step):
+        ap.error("--step takes values of at least 2")
 
     import torch
     from e2sar_amd import sar, _capi
@@ -116,6 +175,7 @@ def main():
     g.manual_seed(1234)
     src = torch.randint(0, 256, (E, (B + 255) // 256 * 256), dtype=torch.uint8, device=dev, generator=g)
     result = {"tool": "rows_bench", "events": E, "event_bytes": B, "reps": args.reps,
+              "step": args.step, "landing": args.landing if args.step else None,
               "lib": os.path.basename(_capi.LIB_PATH), "device": torch.cuda.get_device_name(0), "mtu": {}}
     for mtu in (int(m) for m in args.mtus.split(",")):
         result["mtu"][str(mtu)] = batch(ctx, args, mtu, src, torch, sar)
