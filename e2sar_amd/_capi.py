@@ -193,7 +193,17 @@ class Rows(C.Structure):
     ]
 
 
+class RowsSeen(C.Structure):
+    """e2sar_hip_rows_seen: the fragment bits of a rows window fed through the seen calls."""
+    _fields_ = [
+        ("d_seen", C.c_uint64),
+        ("fragBytes", C.c_uint32),    # the sender's payload per datagram
+        ("maxFrags", C.c_uint32),     # bits per cell, a multiple of 128
+    ]
+
+
 ROWS_MAX_IDS = 64
+ROWS_SEEN_FRAGS_UNIT = 128    # RowsSeen.maxFrags is a multiple of this: a cell's bits are whole 16-byte stores
 ROWS_COMPLETE = 1             # RowsCell.flags: curBytes reached the event's length
 ROWS_TRUNCATED = 2            # ... a fragment passed the pitch
 ROWS_ACC_FRAG_SHIFT = 36      # RowsCell.acc: curBytes below, fragments above
@@ -264,7 +274,7 @@ assert C.sizeof(LostRec) == 24
 assert C.sizeof(CollectRec) == 32
 assert C.sizeof(BuiltRec) == 32
 assert C.sizeof(TurnMarks) == 24
-assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 64
+assert C.sizeof(RowsCell) == 16 and C.sizeof(Rows) == 64 and C.sizeof(RowsSeen) == 16
 assert C.sizeof(RowsReadyRule) == 24 and C.sizeof(RowsEvent) == 32
 
 vp = C.c_void_p
@@ -313,6 +323,10 @@ SIGNATURES = {
     "e2sar_hip_rows_reassemble": (i, [vp, C.POINTER(Rows), vp, u32, vp, vp, u32, vp]),
     "e2sar_hip_rows_advance": (i, [vp, C.POINTER(Rows), vp, u32, vp]),
     "e2sar_hip_rows_clear": (i, [vp, C.POINTER(Rows), u64, vp]),
+    "e2sar_hip_rows_seen_bytes": (sz, [u32, u32, u32]),
+    "e2sar_hip_rows_reassemble_seen": (i, [vp, C.POINTER(Rows), C.POINTER(RowsSeen), vp, u32, vp, vp, u32, vp]),
+    "e2sar_hip_rows_advance_seen": (i, [vp, C.POINTER(Rows), C.POINTER(RowsSeen), vp, u32, vp]),
+    "e2sar_hip_rows_clear_seen": (i, [vp, C.POINTER(Rows), C.POINTER(RowsSeen), u64, vp]),
     "e2sar_hip_rows_ready_work_bytes": (sz, [u32]),
     "e2sar_hip_rows_ready": (i, [vp, C.POINTER(Rows), C.POINTER(RowsReadyRule), vp, vp, vp, sz, vp]),
     "e2sar_hip_relay_plan": (i, [vp, u32, u32, sz, u64, C.c_uint16, vp, vp, vp]),

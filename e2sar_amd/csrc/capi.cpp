@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "e2sar_hip.h"
+#include "rows_div.hpp"
 #include "sar_kernels.hpp"
 
 using namespace e2sar_amd;
@@ -683,6 +684,19 @@ static int check_rows(const e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, RowsDev
     return E2SAR_HIP_OK;
 }
 
+// The seen calls: check_rows, then the bits' descriptor.  Fills the kernels' view of both.
+static int check_rows_seen(const e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen, RowsDev &W,
+                           RowsSeenDev &Z)
+{
+    if (int rc = check_rows(ctx, w, W)) return rc;
+    if (!seen || !seen->d_seen) return fail(E2SAR_HIP_ERR_PARAMETER, "seen descriptor or d_seen is NULL");
+    if (seen->fragBytes == 0) return fail(E2SAR_HIP_ERR_PARAMETER, "fragBytes must be above 0");
+    if (seen->maxFrags == 0 || (seen->maxFrags & 127u)) return fail(E2SAR_HIP_ERR_PARAMETER, "maxFrags must be a multiple of 128");
+    if ((uintptr_t)seen->d_seen & 15u) return fail(E2SAR_HIP_ERR_PARAMETER, "d_seen must be 16-byte aligned");
+    Z = RowsSeenDev{seen->d_seen, rows_div_magic(seen->fragBytes), seen->fragBytes, seen->maxFrags};
+    return E2SAR_HIP_OK;
+}
+
 extern "C" {
 
 int e2sar_hip_rows_reassemble(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const uint8_t *d_packets, uint32_t stride,
@@ -716,6 +730,54 @@ int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t e
     if (W.step > 1u && eventBase % W.step != W.phase)
         return fail(E2SAR_HIP_ERR_PARAMETER, "eventBase mod eventStep must be eventPhase");
     return ctx_call(ctx, stream, "rows clear launch", [&](hipStream_t s) { return launch_rows_clear(W, eventBase, s); });
+}
+
+size_t e2sar_hip_rows_seen_bytes(uint32_t nEvents, uint32_t nIds, uint32_t maxFrags)
+{
+    return (size_t)nEvents * nIds * (maxFrags / 8u);
+}
+
+int e2sar_hip_rows_reassemble_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen,
+                                   const uint8_t *d_packets, uint32_t stride, const uint32_t *d_lens, const uint32_t *d_count,
+                                   uint32_t maxPackets, void *stream)
+{
+    RowsDev W;
+    RowsSeenDev Z;
+    if (!ctx) return fail(E2SAR_HIP_ERR_PARAMETER, "ctx is NULL");
+    if (!w || !d_packets || !d_lens) return fail(E2SAR_HIP_ERR_PARAMETER, "NULL descriptor or device buffer");
+    if (int rc = check_rows_seen(ctx, w, seen, W, Z)) return rc;
+    if (int rc = check_slots(W.withLB != 0, d_packets, stride, maxPackets)) return rc;
+    if (maxPackets == 0) return E2SAR_HIP_OK;
+    return ctx_call(ctx, stream, "rows seen reassembly launch", [&](hipStream_t s) -> int {
+        if (rows_seen_grid(maxPackets, stride, W.step > 1u) > 0x7FFFFFFFull)
+            return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "launch too large (workgroups of maxPackets)");
+        const hipError_t e = launch_rows_seen(W, Z, d_packets, stride, d_lens, d_count, maxPackets, s);
+        return e == hipSuccess ? E2SAR_HIP_OK : hip_fail(e, "rows seen reassembly launch");
+    });
+}
+
+int e2sar_hip_rows_advance_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen, const uint32_t *d_k,
+                                uint32_t kMax, void *stream)
+{
+    RowsDev W;
+    RowsSeenDev Z;
+    if (int rc = check_rows_seen(ctx, w, seen, W, Z)) return rc;
+    if (rows_release_seen_grid(W, Z, kMax) > 0x7FFFFFFFull)
+        return fail(E2SAR_HIP_ERR_OUT_OF_RANGE, "release launch too large (16-byte words of kMax x nIds cells' bits)");
+    return ctx_call(ctx, stream, "rows seen advance launch",
+                    [&](hipStream_t s) { return launch_rows_advance_seen(W, Z, d_k, kMax, s); });
+}
+
+int e2sar_hip_rows_clear_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen, uint64_t eventBase,
+                              void *stream)
+{
+    RowsDev W;
+    RowsSeenDev Z;
+    if (int rc = check_rows_seen(ctx, w, seen, W, Z)) return rc;
+    if (W.step > 1u && eventBase % W.step != W.phase)
+        return fail(E2SAR_HIP_ERR_PARAMETER, "eventBase mod eventStep must be eventPhase");
+    return ctx_call(ctx, stream, "rows seen clear launch",
+                    [&](hipStream_t s) { return launch_rows_clear_seen(W, Z, eventBase, s); });
 }
 
 size_t e2sar_hip_rows_ready_work_bytes(uint32_t nEvents) { return rows_ready_work_bytes(nEvents); }

@@ -1,10 +1,13 @@
 // reas_rows.hpp -- reassembly straight into a dense [events, sources, pitch] tensor (e2sar_hip_rows_*): no table, no arena.
 #pragma once
 
+#include <type_traits>
+
 #include "dev_access.hpp"
 #include "reas_classify.hpp"
 #include "reas_copy.hpp"
 #include "reas_store.hpp"
+#include "rows_div.hpp"
 #include "wire.hpp"
 
 namespace e2sar_amd {
@@ -20,6 +23,10 @@ namespace e2sar_amd {
 // the event's index eventNum / S, and a datagram of another rank's event is passed over at the
 // price of its header -- every wave learns that before it issues a payload load (rows_range).
 // LAT = false is the consecutive window: its code does not know the lattice.
+//   The seen calls (e2sar_hip_rows_reassemble_seen, the template parameter SEEN) keep one bit per fragment of a
+// cell -- fragment f = bufferOffset / fragBytes -- and take a fragment once: between the head's compare-and-swap
+// and the tail's add stands one test-and-set of the bits, an atomicOr per stretch of a run inside one 32-bit
+// word.  SEEN = false is the plain call: its code does not know the bits.
 
 static_assert(sizeof(e2sar_hip_rows_cell) == 16 && offsetof(e2sar_hip_rows_cell, bytes) == 8 &&
                   offsetof(e2sar_hip_rows_cell, flags) == 12,
@@ -29,17 +36,24 @@ static_assert(sizeof(e2sar_hip_rows_cell) == 16 && offsetof(e2sar_hip_rows_cell,
 enum : uint32_t {
     kRowsComplete = 0, kRowsAccepted = 1, kRowsBytes = 2, kRowsLate = 3, kRowsEarly = 4, kRowsForeign = 5,
     kRowsBadHeader = 6, kRowsDataErr = 7, kRowsReleased = 8, kRowsReleasedComplete = 9,
-    kRowsNotOwned = 10             // a lattice only: another rank's event
+    kRowsNotOwned = 10,            // a lattice only: another rank's event
+    kRowsDuplicate = 11            // the seen calls only: a fragment whose bit was set
 };
 
 // Per-workgroup LDS: destinations of the group's datagrams, and what the run tails need
 // after the copy (only the add's return value stays in a register meanwhile).
-template <bool LAT = false>
+template <bool LAT = false, bool SEEN = false>
 struct RowsGroupLds {
     PktInfo info[64];
     uint32_t cell[64], bytes[64], rb[64], tail[64];
-    uint64_t cnt[LAT ? 9 : 8];     // the group's additions to counts[0..7] ([0]: known after the copy); [8]: to counts[10]
+    // the group's additions to counts[0..7] ([0]: known after the copy); a lattice: one more, to counts[10]; the
+    // seen calls: one more behind that, to counts[11]
+    uint64_t cnt[8 + (LAT ? 1 : 0) + (SEEN ? 1 : 0)];
 };
+// What the seen calls add to a window, and what stands in its place in a plain call's kernel arguments: nothing
+struct RowsNoSeen {};
+template <bool SEEN>
+using RowsSeenArg = std::conditional_t<SEEN, RowsSeenDev, RowsNoSeen>;
 static_assert(sizeof(RowsGroupLds<false>) == 2112, "the consecutive window's LDS is what it was");
 
 // The lattice of a window with eventStep S > 1: the index eventNum / S of an event, and whether
@@ -85,9 +99,9 @@ __device__ __forceinline__ void rows_count(uint64_t *counts, uint32_t k, bool on
 // below gn): the rules of e2sar_hip_rows_reassemble in their order.  Leaves every
 // datagram's destination in L.info, the run tails' state and the group's counts in L; returns
 // the value the tail's accumulator add found (consumed after the copy, rows_finish).
-template <bool LAT>
-__device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, const RawHdr &raw, uint32_t stride,
-                                                            bool live, RowsGroupLds<LAT> &L)
+template <bool LAT, bool SEEN>
+__device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, const RowsSeenArg<SEEN> &Z, const RawHdr &raw,
+                                                            uint32_t stride, bool live, RowsGroupLds<LAT, SEEN> &L)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t hl = W.withLB ? kLBREHdrLen : kREHdrLen;
@@ -120,6 +134,17 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
         ok = false;
         derr = true;
     }
+    // the grid of the seen calls (rule 4b): a fragment of more than 0 bytes lies on a multiple of fragBytes, is at
+    // most that long, and its number is below maxFrags; it opens nothing otherwise
+    uint32_t f = 0;
+    if constexpr (SEEN) {
+        const RowsQuot fq = rows_div(h.off, Z.fragBytes, Z.magic);
+        f = fq.q;
+        if (ok && h.pl > 0u && (fq.r != 0u || h.pl > Z.fragBytes || f >= Z.maxFrags)) {
+            ok = false;
+            derr = true;
+        }
+    }
     const uint32_t cell = ok ? ((uint32_t)idx & (W.nEvents - 1u)) * W.nIds + j : ~0u;
 
     // ---- runs of one cell: consecutive lanes of one (eventNum, dataId) inside the window ----
@@ -144,6 +169,31 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
     if (take && (uint64_t)h.off + h.pl > sb) {
         take = false;
         derr = true;
+    }
+    // The seen calls (rule 5b): the fragment's bit, tested and set.  A stretch is a maximal sequence of consecutive
+    // lanes whose fragments have bytes, share one word of the bits and rise in f from lane to lane: its bits are
+    // distinct, so their sum (a scan, as the run sums below) is their union, and the stretch's last lane issues one
+    // returning atomicOr for all of them -- a handful per in-order group, in one instruction, one round trip.  Two
+    // copies of a fragment never share a stretch: their atomics are ordered by the memory system, and exactly
+    // one finds the bit clear.
+    bool dup = false;
+    if constexpr (SEEN) {
+        const bool part = take && h.pl > 0u;
+        const uint64_t wi = part ? (uint64_t)cell * (Z.maxFrags >> 5) + (f >> 5) : ~0ull;
+        const uint64_t pw = ((uint64_t)lane_prev((uint32_t)(wi >> 32), ~0u) << 32) | lane_prev((uint32_t)wi, ~0u);
+        const uint64_t nw = ((uint64_t)lane_next((uint32_t)(wi >> 32), ~0u) << 32) | lane_next((uint32_t)wi, ~0u);
+        const uint32_t pf = lane_prev(f, 0u), nf = lane_next(f, 0u);
+        const bool first = part && (lane == 0u || pw != wi || pf >= f);
+        const bool last = part && (lane == 63u || nw != wi || f >= nf);
+        const uint32_t bit = part ? 1u << (f & 31u) : 0u;
+        const uint32_t is = wave_incl_scan(bit);
+        const uint32_t mask = is - __shfl(is - bit, run_head_lane(__ballot(first), lane));
+        uint32_t was = 0;
+        if (last) was = atomicOr(Z.seen + wi, mask);
+        const uint64_t lasts = __ballot(last) & (~0ull << lane);       // part: its stretch's last lane is at or above it
+        was = __shfl(was, lasts ? __builtin_ctzll(lasts) : (int)lane);
+        dup = part && ((was >> (f & 31u)) & 1u) != 0u;
+        take = take && !dup;
     }
     // segmented sums over the run (inclusive scans, then the difference at the head)
     const uint32_t xb = take ? h.pl : 0u, xc = take ? 1u : 0u;
@@ -179,19 +229,21 @@ __device__ __forceinline__ unsigned long long rows_classify(const RowsDev &W, co
     const uint64_t votes[8] = {0ull, __ballot(take), 0ull, __ballot(late), __ballot(outside && !late), __ballot(foreign),
                                __ballot(h.bad), __ballot(derr)};
     const uint64_t voteNotOwned = LAT ? __ballot(notOwned) : 0ull;
+    const uint64_t voteDup = SEEN ? __ballot(dup) : 0ull;
     if (lane == 0u) {
 #pragma unroll
         for (uint32_t k = 0; k < 8u; k++) L.cnt[k] = (uint64_t)__builtin_popcountll(votes[k]);
         L.cnt[kRowsBytes] = tb;
         if constexpr (LAT) L.cnt[8] = (uint64_t)__builtin_popcountll(voteNotOwned);
+        if constexpr (SEEN) L.cnt[LAT ? 9 : 8] = (uint64_t)__builtin_popcountll(voteDup);
     }
     return old;
 }
 
 // After the copy, by the classifying wave: a tail whose add of more than 0 bytes brought the
 // cell's curBytes to its length marks the cell complete.
-template <bool LAT>
-__device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long old, const RowsGroupLds<LAT> &L)
+template <bool LAT, bool SEEN>
+__device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long old, const RowsGroupLds<LAT, SEEN> &L)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t rb = L.rb[lane];
@@ -199,7 +251,14 @@ __device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long
     if (done) atomicOr(&W.cells[L.cell[lane]].flags, E2SAR_HIP_ROWS_COMPLETE);
     // the workgroup's counts: lane k adds to counts[k], one instruction for all eight
     const uint64_t ndone = (uint64_t)__builtin_popcountll(__ballot(done));
-    if constexpr (LAT) {                                               // lane 8: counts[10]
+    if constexpr (SEEN) {                                              // behind the eight: counts[10] (a lattice), counts[11]
+        constexpr uint32_t nCnt = LAT ? 10u : 9u;
+        if (lane < nCnt) {
+            const uint64_t v = (lane == kRowsComplete) ? ndone : L.cnt[lane];
+            const uint32_t k = lane < 8u ? lane : (lane == nCnt - 1u ? kRowsDuplicate : kRowsNotOwned);
+            if (v) atomicAdd((unsigned long long *)(W.counts + k), (unsigned long long)v);
+        }
+    } else if constexpr (LAT) {                                        // lane 8: counts[10]
         if (lane < 9u) {
             const uint64_t v = (lane == kRowsComplete) ? ndone : L.cnt[lane];
             if (v) atomicAdd((unsigned long long *)(W.counts + (lane < 8u ? lane : kRowsNotOwned)), (unsigned long long)v);
@@ -220,9 +279,10 @@ __device__ __forceinline__ void rows_finish(const RowsDev &W, unsigned long long
 //   4. every thread stores its chunks (da_store), then loads and stores the rest round by
 //      round, the loads of round r + 1 issued before the stores of round r;
 //   5. wave 0's run tails mark completed cells (rows_finish).
-template <int U, int NT, bool LAT>
-__device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__restrict__ pkts, uint32_t stride,
-                                           const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn, RowsGroupLds<LAT> &L)
+template <int U, int NT, bool LAT, bool SEEN>
+__device__ __forceinline__ void rows_range(const RowsDev &W, const RowsSeenArg<SEEN> &Z, const uint8_t *__restrict__ pkts,
+                                           uint32_t stride, const uint32_t *__restrict__ lens, uint32_t g0, uint32_t gn,
+                                           RowsGroupLds<LAT, SEEN> &L)
 {
     const bool w0 = threadIdx.x < 64;
     const uint32_t lane = threadIdx.x & 63u;
@@ -238,25 +298,26 @@ __device__ __forceinline__ void rows_range(const RowsDev &W, const uint8_t *__re
 
     unsigned long long old = 0;
     group_copy<U, false, NT>(pkts, stride, g0, gn, hl, bswap32(raw.re.y) & kPhaseMask, gPlen, L.info,
-                             [&] { if (w0) old = rows_classify<LAT>(W, raw, stride, lane < gn, L); });
+                             [&] { if (w0) old = rows_classify<LAT, SEEN>(W, Z, raw, stride, lane < gn, L); });
 
-    if (w0) rows_finish<LAT>(W, old, L);
+    if (w0) rows_finish<LAT, SEEN>(W, old, L);
 }
 
 // rows_kernel: workgroup b takes datagrams [b*G, b*G + G) of the first n = min(*count,
 // bound) (count NULL: bound); the grid is cdiv(bound, G).  A workgroup at or past n costs the
 // load of one word and an exit (reas_devcount.hpp): no header load, no LDS, no counter.
-// LAT: the window is on a lattice (RowsDev.step > 1).
-template <int U, int NT, bool LAT = false>
+// LAT: the window is on a lattice (RowsDev.step > 1).  SEEN: a seen call; its bits travel in an argument of their
+// own behind the others, where a plain call has an empty one, so that a plain window's kernel reads what it read.
+template <int U, int NT, bool LAT = false, bool SEEN = false>
 __global__ __launch_bounds__(NT) void rows_kernel(RowsDev W, const uint8_t *__restrict__ pkts, uint32_t stride,
                                                   const uint32_t *__restrict__ lens, const uint32_t *__restrict__ count,
-                                                  uint32_t bound, uint32_t G)
+                                                  uint32_t bound, uint32_t G, RowsSeenArg<SEEN> Z)
 {
-    __shared__ RowsGroupLds<LAT> L;
+    __shared__ RowsGroupLds<LAT, SEEN> L;
     const uint32_t n = count ? dev_count(count, bound) : bound;
     const uint64_t g0 = (uint64_t)blockIdx.x * G;
     if (g0 >= n) return;
-    rows_range<U, NT, LAT>(W, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);
+    rows_range<U, NT, LAT, SEEN>(W, Z, pkts, stride, lens, (uint32_t)g0, (n - (uint32_t)g0 < G) ? n - (uint32_t)g0 : G, L);
 }
 
 // ---------------------------------------------------------------------------------
@@ -295,6 +356,34 @@ __global__ __launch_bounds__(kBlock) void rows_release_kernel(RowsDev W, const u
     rows_count(W.counts, kRowsReleasedComplete, complete);
 }
 
+// The seen calls' release: thread t < k * nIds * Q, Q = maxFrags / 128 the 16-byte words of a cell's bits, zeroes
+// word t % Q of the cell t / Q (numbered as above); the thread of word 0 also counts and zeroes the cell, as
+// rows_release_kernel does.  Grid: cdiv(min(kMax, nEvents) * nIds * Q, kBlock).
+__global__ __launch_bounds__(kBlock) void rows_release_seen_kernel(RowsDev W, RowsSeenDev Z, const uint32_t *__restrict__ d_k,
+                                                                  uint32_t kMax)
+{
+    const uint64_t k = rows_advance_k(W, d_k, kMax);
+    const uint64_t Q = Z.maxFrags >> 7;
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool in = t < k * W.nIds * Q;
+    bool open = false, complete = false;
+    if (in) {
+        const uint64_t u = t / Q, wq = t - u * Q;
+        const uint64_t e = u / W.nIds;
+        const uint64_t c = ((rows_base_index(W) + e) & (uint64_t)(W.nEvents - 1u)) * W.nIds + (u - e * W.nIds);
+        if (wq == 0u) {
+            uint8_t *cp = reinterpret_cast<uint8_t *>(W.cells + c);
+            const u32x4 v = ld16(cp);
+            complete = (v.w & E2SAR_HIP_ROWS_COMPLETE) != 0u;
+            open = v.z != 0u && !complete;
+            st16(cp, u32x4{0u, 0u, 0u, 0u});
+        }
+        st16(reinterpret_cast<uint8_t *>(Z.seen) + (c * Q + wq) * 16u, u32x4{0u, 0u, 0u, 0u});
+    }
+    rows_count(W.counts, kRowsReleased, open);
+    rows_count(W.counts, kRowsReleasedComplete, complete);
+}
+
 __global__ __launch_bounds__(64) void rows_shift_kernel(RowsDev W, const uint32_t *__restrict__ d_k, uint32_t kMax)
 {
     if (threadIdx.x == 0) *W.base += rows_advance_k(W, d_k, kMax) * rows_stride(W);
@@ -307,6 +396,20 @@ __global__ __launch_bounds__(kBlock) void rows_clear_kernel(RowsDev W, uint64_t 
     const uint64_t nCells = (uint64_t)W.nEvents * W.nIds;
     for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nCells; c += (uint64_t)gridDim.x * kBlock)
         st16(reinterpret_cast<uint8_t *>(W.cells + c), u32x4{0u, 0u, 0u, 0u});
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < 16u) W.counts[threadIdx.x] = 0ull;
+        if (threadIdx.x == 16u) *W.base = eventBase;
+    }
+}
+
+// The seen calls' clear: rows_clear_kernel, and every 16-byte word of the bits zeroed.
+__global__ __launch_bounds__(kBlock) void rows_clear_seen_kernel(RowsDev W, RowsSeenDev Z, uint64_t eventBase)
+{
+    const uint64_t nCells = (uint64_t)W.nEvents * W.nIds, nWords = nCells * (Z.maxFrags >> 7);
+    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nCells; c += (uint64_t)gridDim.x * kBlock)
+        st16(reinterpret_cast<uint8_t *>(W.cells + c), u32x4{0u, 0u, 0u, 0u});
+    for (uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x; q < nWords; q += (uint64_t)gridDim.x * kBlock)
+        st16(reinterpret_cast<uint8_t *>(Z.seen) + q * 16u, u32x4{0u, 0u, 0u, 0u});
     if (blockIdx.x == 0) {
         if (threadIdx.x < 16u) W.counts[threadIdx.x] = 0ull;
         if (threadIdx.x == 16u) *W.base = eventBase;

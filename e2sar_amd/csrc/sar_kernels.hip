@@ -459,13 +459,15 @@ hipError_t launch_reassemble(const ReasDev &R, const uint8_t *pkts, uint32_t str
 
 // The launch's geometry for a bound of maxPackets: G datagrams per workgroup -- reas_kernel's
 // rule (reas_group_size), balanced over this kernel's residency; returns the grid.
-// lattice: the window's eventStep is above 1, and the kernel is the instantiation that knows it.
-static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, bool lattice, uint32_t &G)
+// lattice: the window's eventStep is above 1; seen: a seen call -- the kernel is the instantiation that knows either.
+static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, bool lattice, bool seen, uint32_t &G)
 {
     with_reas_threads(stride, [&](auto nt) {
         constexpr int NT = decltype(nt)::value;
-        G = lattice ? reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT, true>, NT>)
-                    : reas_group_size(maxPackets, stride, 0u, resident_groups<rows_kernel<kReasU, NT>, NT>);
+        uint32_t (*const resident[4])() = {
+            resident_groups<rows_kernel<kReasU, NT>, NT>, resident_groups<rows_kernel<kReasU, NT, true>, NT>,
+            resident_groups<rows_kernel<kReasU, NT, false, true>, NT>, resident_groups<rows_kernel<kReasU, NT, true, true>, NT>};
+        G = reas_group_size(maxPackets, stride, 0u, resident[(seen ? 2 : 0) + (lattice ? 1 : 0)]);
     });
     return ((uint64_t)maxPackets + G - 1u) / G;
 }
@@ -473,28 +475,44 @@ static uint64_t rows_geometry(uint32_t maxPackets, uint32_t stride, bool lattice
 uint64_t rows_grid(uint32_t maxPackets, uint32_t stride, bool lattice)
 {
     uint32_t G = 1;
-    return rows_geometry(maxPackets, stride, lattice, G);
+    return rows_geometry(maxPackets, stride, lattice, false, G);
+}
+uint64_t rows_seen_grid(uint32_t maxPackets, uint32_t stride, bool lattice)
+{
+    uint32_t G = 1;
+    return rows_geometry(maxPackets, stride, lattice, true, G);
+}
+
+// One launch of rows_kernel<., ., LAT, SEEN>; Z is the seen calls' argument, or the plain calls' empty one
+template <bool LAT, bool SEEN>
+static hipError_t launch_rows_as(const RowsDev &W, const RowsSeenArg<SEEN> &Z, const uint8_t *pkts, uint32_t stride,
+                                 const uint32_t *lens, const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream)
+{
+    constexpr int U = kReasU;
+    if (maxPackets == 0) return hipSuccess;
+    uint32_t G = 1;
+    const uint64_t grid = rows_geometry(maxPackets, stride, LAT, SEEN, G);
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    with_reas_threads(stride, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        hipLaunchKernelGGL((rows_kernel<U, NT, LAT, SEEN>), dim3((uint32_t)grid), dim3(NT),
+                           reas_lds<NT>(rows_kernel<U, NT, LAT, SEEN>), stream, W, pkts, stride, lens, d_count, maxPackets, G, Z);
+    });
+    return hipGetLastError();
 }
 
 hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
                        const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream)
 {
-    constexpr int U = kReasU;
-    if (maxPackets == 0) return hipSuccess;
-    uint32_t G = 1;
-    const bool lattice = W.step > 1u;
-    const uint64_t grid = rows_geometry(maxPackets, stride, lattice, G);
-    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    with_reas_threads(stride, [&](auto nt) {
-        constexpr int NT = decltype(nt)::value;
-        if (lattice)
-            hipLaunchKernelGGL((rows_kernel<U, NT, true>), dim3((uint32_t)grid), dim3(NT),
-                               reas_lds<NT>(rows_kernel<U, NT, true>), stream, W, pkts, stride, lens, d_count, maxPackets, G);
-        else
-            hipLaunchKernelGGL((rows_kernel<U, NT>), dim3((uint32_t)grid), dim3(NT), reas_lds<NT>(rows_kernel<U, NT>), stream, W,
-                               pkts, stride, lens, d_count, maxPackets, G);
-    });
-    return hipGetLastError();
+    return W.step > 1u ? launch_rows_as<true, false>(W, RowsNoSeen{}, pkts, stride, lens, d_count, maxPackets, stream)
+                       : launch_rows_as<false, false>(W, RowsNoSeen{}, pkts, stride, lens, d_count, maxPackets, stream);
+}
+
+hipError_t launch_rows_seen(const RowsDev &W, const RowsSeenDev &Z, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                            const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream)
+{
+    return W.step > 1u ? launch_rows_as<true, true>(W, Z, pkts, stride, lens, d_count, maxPackets, stream)
+                       : launch_rows_as<false, true>(W, Z, pkts, stride, lens, d_count, maxPackets, stream);
 }
 
 hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t kMax, hipStream_t stream)
@@ -502,6 +520,26 @@ hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t k
     const uint64_t cells = (uint64_t)(kMax < W.nEvents ? kMax : W.nEvents) * W.nIds;     // <= 2^32 - 1
     if (cells == 0) return hipSuccess;
     hipLaunchKernelGGL(rows_release_kernel, dim3(cdiv(cells, kBlock)), dim3(kBlock), 0, stream, W, d_k, kMax);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rows_shift_kernel, dim3(1), dim3(64), 0, stream, W, d_k, kMax);
+    return hipGetLastError();
+}
+
+// cdiv(min(kMax, nEvents) * nIds * (maxFrags / 128), kBlock): the workgroups of rows_release_seen_kernel
+uint64_t rows_release_seen_grid(const RowsDev &W, const RowsSeenDev &Z, uint32_t kMax)
+{
+    const uint64_t words = (uint64_t)(kMax < W.nEvents ? kMax : W.nEvents) * W.nIds * (Z.maxFrags >> 7);  // < 2^57
+    return (words + kBlock - 1u) / kBlock;
+}
+
+hipError_t launch_rows_advance_seen(const RowsDev &W, const RowsSeenDev &Z, const uint32_t *d_k, uint32_t kMax,
+                                    hipStream_t stream)
+{
+    const uint64_t grid = rows_release_seen_grid(W, Z, kMax);
+    if (grid == 0) return hipSuccess;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rows_release_seen_kernel, dim3((uint32_t)grid), dim3(kBlock), 0, stream, W, Z, d_k, kMax);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rows_shift_kernel, dim3(1), dim3(64), 0, stream, W, d_k, kMax);
@@ -537,6 +575,14 @@ hipError_t launch_rows_clear(const RowsDev &W, uint64_t eventBase, hipStream_t s
 {
     const uint64_t blocks = ((uint64_t)W.nEvents * W.nIds + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(rows_clear_kernel, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, stream, W,
+                       eventBase);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_clear_seen(const RowsDev &W, const RowsSeenDev &Z, uint64_t eventBase, hipStream_t stream)
+{
+    const uint64_t blocks = ((uint64_t)W.nEvents * W.nIds * (Z.maxFrags >> 7) + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(rows_clear_seen_kernel, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, stream, W, Z,
                        eventBase);
     return hipGetLastError();
 }

@@ -327,6 +327,13 @@ struct RowsDev {
     uint64_t magic;
     uint32_t step, phase;
 };
+// What the seen calls add to a window (e2sar_hip_rows_seen), a kernel argument of its own: a plain window's
+// kernels do not know it.  magic = rows_div_magic(fragBytes), the host's multiplier for bufferOffset / fragBytes.
+struct RowsSeenDev {
+    uint32_t *seen;                // maxFrags bits per cell, cell c at word c * maxFrags / 32; 16-byte aligned
+    uint64_t magic;
+    uint32_t fragBytes, maxFrags;  // maxFrags a multiple of 128
+};
 // rows_kernel over n = min(*d_count, maxPackets) datagrams (d_count NULL: maxPackets): its
 // grid, from maxPackets and the stride alone (above 2^31 - 1: no launch is possible), and the
 // one launch; lattice: W.step > 1 (another instantiation, its own residency)
@@ -336,6 +343,16 @@ hipError_t launch_rows(const RowsDev &W, const uint8_t *pkts, uint32_t stride, c
 // rows_release_kernel, then rows_shift_kernel; and rows_clear_kernel
 hipError_t launch_rows_advance(const RowsDev &W, const uint32_t *d_k, uint32_t kMax, hipStream_t stream);
 hipError_t launch_rows_clear(const RowsDev &W, uint64_t eventBase, hipStream_t stream);
+// The seen calls: rows_kernel's instantiations that test and set a fragment's bit (their own residency, so their
+// own grid); rows_release_seen_kernel, whose grid (rows_release_seen_grid, from the descriptors and kMax alone)
+// must not exceed 2^31 - 1, then rows_shift_kernel; and rows_clear_seen_kernel
+uint64_t rows_seen_grid(uint32_t maxPackets, uint32_t stride, bool lattice);
+hipError_t launch_rows_seen(const RowsDev &W, const RowsSeenDev &Z, const uint8_t *pkts, uint32_t stride, const uint32_t *lens,
+                            const uint32_t *d_count, uint32_t maxPackets, hipStream_t stream);
+uint64_t rows_release_seen_grid(const RowsDev &W, const RowsSeenDev &Z, uint32_t kMax);
+hipError_t launch_rows_advance_seen(const RowsDev &W, const RowsSeenDev &Z, const uint32_t *d_k, uint32_t kMax,
+                                    hipStream_t stream);
+hipError_t launch_rows_clear_seen(const RowsDev &W, const RowsSeenDev &Z, uint64_t eventBase, hipStream_t stream);
 // e2sar_hip_rows_ready: rows_scan_kernel, rows_ready_kernel and, with `zero`, rows_zero_kernel, whose grid
 // (rows_zero_grid, from the descriptor and kMax alone) must not exceed 2^31 - 1; `required` is not 0; d_work holds
 // rows_ready_work_bytes(nEvents)

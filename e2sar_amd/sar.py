@@ -672,16 +672,43 @@ class RowWindow:
     event is (eventNum // S) mod n_events, and a datagram of another rank's event is passed over
     at the price of its header and counted in counts[10].  advance(), ready()'s slack and k_max
     then count positions, that is owned events.  Event numbers do not wrap on such a window.
+
+    With frag_bytes (the sender's payload per datagram, the Segmenter's maxPld) the window survives
+    duplicates: it also owns `seen` (int32, max_frags bits per cell), reassemble(), advance() and
+    clear() go to the e2sar_hip_rows_*_seen calls, a fragment that arrives twice is taken once and
+    counted in counts[11], and a COMPLETE cell has had every byte of its row's event written.
+    max_frags (a multiple of 128) defaults to the fragments of `pitch` bytes, rounded up; an event
+    longer than the pitch needs more to complete.
     """
 
+    @staticmethod
+    def seen_frags(pitch: int, frag_bytes: Optional[int], max_frags: Optional[int] = None) -> int:
+        """The max_frags of a window: the argument checks of frag_bytes= and max_frags=, and the
+        default -- cdiv(pitch, frag_bytes) rounded up to a multiple of 128.  0 without frag_bytes."""
+        unit = _capi.ROWS_SEEN_FRAGS_UNIT
+        if frag_bytes is None:
+            if max_frags is not None:
+                raise ValueError("max_frags needs frag_bytes")
+            return 0
+        if not 0 < int(frag_bytes) < 1 << 32:
+            raise ValueError("frag_bytes must be in [1, 2^32)")
+        if max_frags is None:
+            return -(-(-(-int(pitch) // int(frag_bytes))) // unit) * unit
+        if not 0 < int(max_frags) < 1 << 32 or int(max_frags) % unit:
+            raise ValueError("max_frags must be a multiple of 128 in (0, 2^32)")
+        return int(max_frags)
+
     def __init__(self, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, event_base: int = 0,
-                 with_lb_header: bool = True, step: int = 1, phase: int = 0):
+                 with_lb_header: bool = True, step: int = 1, phase: int = 0, frag_bytes: Optional[int] = None,
+                 max_frags: Optional[int] = None):
         ids = [int(d) for d in ids]
         if not ids or len(ids) > _capi.ROWS_MAX_IDS:
             raise ValueError("a RowWindow names 1..64 dataIds")
         self.step, self.phase = int(step), int(phase)
         if self.step > 1 and (int(event_base) & 0xFFFFFFFFFFFFFFFF) % self.step != self.phase:
             raise ValueError("event_base % step must be phase")
+        self.max_frags = self.seen_frags(pitch, frag_bytes, max_frags)
+        self.frag_bytes = None if frag_bytes is None else int(frag_bytes)
         self.ctx = ctx
         self.ids = ids
         self.n_events = int(n_events)
@@ -695,7 +722,18 @@ class RowWindow:
         self._ids = (C.c_uint16 * len(ids))(*ids)
         self._w = _capi.Rows(self.out.data_ptr(), self.cells.data_ptr(), self.base.data_ptr(), self.counts.data_ptr(),
                              self._ids, len(ids), self.n_events, self.pitch, 1 if with_lb_header else 0, self.step, self.phase)
+        self.seen, self._seen = None, None
+        if self.frag_bytes is not None:
+            self.seen = torch.empty(self.n_events * len(ids) * (self.max_frags // 32), dtype=torch.int32, device=dev)
+            self._seen = _capi.RowsSeen(self.seen.data_ptr(), self.frag_bytes, self.max_frags)
         self.clear(event_base)
+
+    def _rows_call(self, name: str, *args) -> None:
+        """e2sar_hip_rows_<name>(ctx, w, ...), or with frag_bytes e2sar_hip_rows_<name>_seen(ctx, w, seen, ...)."""
+        if self._seen is None:
+            _call("e2sar_hip_rows_" + name, self.ctx.handle, C.byref(self._w), *args)
+        else:
+            _call("e2sar_hip_rows_" + name + "_seen", self.ctx.handle, C.byref(self._w), C.byref(self._seen), *args)
 
     @staticmethod
     def first_owned(first_event: int, world: int, rank: int) -> int:
@@ -708,11 +746,12 @@ class RowWindow:
 
     @classmethod
     def for_rank(cls, ctx: Context, ids: Sequence[int], n_events: int, pitch: int, world: int, rank: int,
-                 first_event: int = 0, with_lb_header: bool = True) -> "RowWindow":
+                 first_event: int = 0, with_lb_header: bool = True, frag_bytes: Optional[int] = None,
+                 max_frags: Optional[int] = None) -> "RowWindow":
         """The window of rank `rank` of `world` on a stream that starts at first_event: step world,
         phase rank, its base the rank's first event (first_owned)."""
         return cls(ctx, ids, n_events, pitch, cls.first_owned(first_event, world, rank), with_lb_header,
-                   step=world, phase=rank)
+                   step=world, phase=rank, frag_bytes=frag_bytes, max_frags=max_frags)
 
     def reassemble(self, packets: torch.Tensor, stride: int, lens: torch.Tensor, max_packets: int,
                    count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
@@ -724,8 +763,7 @@ class RowWindow:
         if count is not None and count.numel() < 1:
             raise ValueError("count is empty")
         _need_batch("packet batch buffers too small for max_packets", max_packets, stride, packets, lens)
-        _call("e2sar_hip_rows_reassemble", self.ctx.handle, C.byref(self._w), packets.data_ptr(), stride, lens.data_ptr(),
-              _p(count), max_packets, _s(stream))
+        self._rows_call("reassemble", packets.data_ptr(), stride, lens.data_ptr(), _p(count), max_packets, _s(stream))
 
     def advance(self, k: int, count: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Let go of the min(count[0], k, n_events) oldest events (positions of the window) -- min(k, n_events) when
@@ -734,12 +772,12 @@ class RowWindow:
         (e2sar_hip_rows_advance).  No host read, capturable."""
         if count is not None and (count.dtype != torch.int32 or count.numel() < 1):
             raise ValueError("count is an int32 tensor of at least 1")
-        _call("e2sar_hip_rows_advance", self.ctx.handle, C.byref(self._w), _p(count), int(k), _s(stream))
+        self._rows_call("advance", _p(count), int(k), _s(stream))
 
     def clear(self, event_base: int = 0, stream: Optional[torch.cuda.Stream] = None) -> None:
         """Every cell and count zeroed, the window at [event_base, event_base + n_events)
         (e2sar_hip_rows_clear; on a lattice event_base % step must be phase); row bytes stay."""
-        _call("e2sar_hip_rows_clear", self.ctx.handle, C.byref(self._w), int(event_base) & 0xFFFFFFFFFFFFFFFF, _s(stream))
+        self._rows_call("clear", int(event_base) & 0xFFFFFFFFFFFFFFFF, _s(stream))
 
     def alloc_ready(self, k_max: int) -> None:
         """Give the window what ready() writes: `ready` (int32[8], read as uint32), `events`
@@ -786,6 +824,15 @@ class RowWindow:
         torch.cuda.synchronize(self.cells.device)
         raw = self.cells.cpu().numpy().tobytes()
         return np.frombuffer(raw, ROWS_CELL).reshape(self.n_events, len(self.ids)).copy()
+
+    def parse_seen(self) -> np.ndarray:
+        """The fragment bits of a window with frag_bytes on the host, uint32 of shape
+        [n_events, n_ids, max_frags // 32] -- bit f of a cell in word f // 32 at 1 << (f % 32):
+        waits for the device and copies."""
+        if self.seen is None:
+            raise ValueError("a window without frag_bytes keeps no bits")
+        torch.cuda.synchronize(self.seen.device)
+        return self.seen.cpu().numpy().view(np.uint32).reshape(self.n_events, len(self.ids), self.max_frags // 32).copy()
 
     def parse_counts(self):
         """-> (the 16 counts, the base), as Python integers: waits for the device and copies."""

@@ -682,7 +682,8 @@ int e2sar_hip_seg_emit(e2sar_hip_ctx *ctx, const e2sar_hip_seg_source *src,
 /* accepted, [2] their payload bytes, [3] late (behind the window), [4] early (ahead of   */
 /* it), [5] foreign dataId, [6] bad header, [7] data error, [8] cells released incomplete */
 /* by advance, [9] cells released complete, [10] datagrams of events the window does not   */
-/* own (a lattice only, below); [11..15] reserved, written only by clear.                 */
+/* own (a lattice only, below); [11] duplicates (the seen calls only, below); [12..15]      */
+/* reserved, written only by clear.                                                       */
 /*   The lattice.  Events are sharded over W consumers by eventNum mod W (the multi-GPU    */
 /* section below); the window of consumer r holds its share, not every event number.      */
 /* With eventStep = S > 1 and eventPhase = P < S, position i of the window holds event    */
@@ -752,7 +753,8 @@ typedef struct e2sar_hip_rows {
 /* fragment arrives twice and each cell has one determinate opener within a launch (all   */
 /* its fragments in the launch announce one length, or the cell was opened by an earlier  */
 /* launch).  Unlike the reference, an offset-0 fragment is not special, a bufferLength of */
-/* 0 is a data error, and nothing is logged as lost: see e2sar_hip_rows_advance.          */
+/* 0 is a data error, and nothing is logged as lost: see e2sar_hip_rows_advance.  A       */
+/* stream that may repeat a fragment goes through e2sar_hip_rows_reassemble_seen (below). */
 /*   Flags and lengths are for launches ordered after this one.                           */
 /* Status: PARAMETER for a NULL ctx, w, d_packets or d_lens, a NULL d_out, d_cells,       */
 /* d_base, d_counts or dataIds, nIds 0 or above 64 or a repeated id, nEvents 0 or not a   */
@@ -782,6 +784,70 @@ int e2sar_hip_rows_advance(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const ui
 /* One launch of plain stores (no memset node), capturable.  Status as above, and         */
 /* PARAMETER for an eventBase with eventBase mod eventStep != eventPhase (eventStep > 1). */
 int e2sar_hip_rows_clear(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, uint64_t eventBase, void *stream);
+
+/* The seen calls: a window that survives duplicates.  The calls above complete a cell    */
+/* when curBytes reaches S, and a fragment that arrives twice is added twice: a duplicate */
+/* together with a lost fragment of the same length marks a cell COMPLETE with a hole in  */
+/* its row, and a duplicate alone makes curBytes pass S, so that the event never          */
+/* completes.  The three calls below keep one bit per fragment of a cell beside the       */
+/* window and take every fragment once.  The sender cuts an event into fragments of       */
+/* fragBytes payload bytes (the Segmenter's maxPld; the last may be shorter), so fragment */
+/* f = bufferOffset / fragBytes, exact for every 32-bit offset and every fragBytes.  The  */
+/* bits are the caller's, as the rest of the window is: e2sar_hip_rows_seen_bytes(nEvents,*/
+/* nIds, maxFrags) = nEvents * nIds * maxFrags / 8 bytes of device memory, 16-byte        */
+/* aligned, maxFrags bits per cell, the bits of cell c from word c * maxFrags / 32, bit f */
+/* of a cell in its word f / 32 at 1 << (f % 32).  maxFrags is independent of the pitch:  */
+/* an event longer than the pitch still completes, TRUNCATED, if maxFrags * fragBytes     */
+/* covers it.                                                                             */
+/*   e2sar_hip_rows_reassemble_seen is e2sar_hip_rows_reassemble to the letter, on a      */
+/* consecutive window or a lattice, with two more rules:                                  */
+/*   4b. (with rule 4: the fragment's own header, it opens no cell) for a fragment of     */
+/*      more than 0 payload bytes: bufferOffset mod fragBytes != 0, payload > fragBytes   */
+/*      or f >= maxFrags -> counts[7];                                                    */
+/*   5b. (after rule 5) for a fragment of more than 0 payload bytes: if bit f of the cell */
+/*      is set, the datagram is a duplicate -> counts[11]; no byte of it is written, and  */
+/*      acc and the flags do not move.  Otherwise the bit is set and rule 6 accepts the   */
+/*      fragment.  A bit is set only by an accepted fragment.                             */
+/* A fragment of 0 payload bytes is outside the grid and the bits: it is accepted as by   */
+/* the plain call, sets no bit and is never a duplicate.  Of several copies of a fragment */
+/* inside one launch exactly one is accepted, which one is not specified; across launches */
+/* the earlier one wins, and its bytes stay in the row.                                   */
+/*   The guarantee.  The accepted fragments of a cell lie on distinct positions of the    */
+/* grid, each is at most fragBytes long and lies inside [0, S); so curBytes == S implies  */
+/* that every byte of [0, S) was covered: a COMPLETE cell has had every byte of [0,       */
+/* min(bytes, pitch)) of its row written by a fragment of that event.  The proviso "no    */
+/* fragment arrives twice" of e2sar_hip_rows_reassemble is dropped for these calls; the   */
+/* proviso of one determinate opener per cell within a launch stays.                      */
+/*   e2sar_hip_rows_advance_seen is e2sar_hip_rows_advance, and also zeroes the bits of   */
+/* every released cell, in the launch that zeroes the cell; e2sar_hip_rows_clear_seen is  */
+/* e2sar_hip_rows_clear, and also zeroes the bits of every cell.  Stores only, no memset  */
+/* node; the grids come from the descriptors and kMax alone.  All three calls are         */
+/* capturable as their plain forms are: no allocation, no wait, nothing read back.        */
+/* e2sar_hip_rows_ready reads cells only and serves either kind of window.                */
+/*   counts[11] is the number of duplicates; the plain calls never write it outside       */
+/* clear.  A window fed through e2sar_hip_rows_reassemble_seen is advanced and cleared by */
+/* the seen calls only: the plain advance or clear leaves stale bits behind, after which  */
+/* fragments of later events are taken for duplicates.  That is the caller's error and is */
+/* not detected.                                                                          */
+/* Status: the plain call's, and PARAMETER for a NULL seen or d_seen, fragBytes 0,        */
+/* maxFrags 0 or not a multiple of 128, a d_seen that is not 16-byte aligned;             */
+/* OUT_OF_RANGE where a launch would pass 2^31 - 1 workgroups (reassemble_seen: of        */
+/* maxPackets; advance_seen: 256 16-byte words of the bits of min(kMax, nEvents) * nIds   */
+/* cells each).                                                                           */
+typedef struct e2sar_hip_rows_seen {
+    uint32_t *d_seen;    /* device, e2sar_hip_rows_seen_bytes(...) bytes, 16-byte aligned: maxFrags bits per cell, cell c at word c * maxFrags / 32 */
+    uint32_t fragBytes;  /* the sender's payload per datagram (the Segmenter's maxPld); > 0 */
+    uint32_t maxFrags;   /* fragments tracked per cell; > 0, a multiple of 128 (a cell's bits are whole 16-byte stores) */
+} e2sar_hip_rows_seen;   /* 16 bytes */
+
+size_t e2sar_hip_rows_seen_bytes(uint32_t nEvents, uint32_t nIds, uint32_t maxFrags);
+int e2sar_hip_rows_reassemble_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen,
+                                   const uint8_t *d_packets, uint32_t stride, const uint32_t *d_lens,
+                                   const uint32_t *d_count, uint32_t maxPackets, void *stream);
+int e2sar_hip_rows_advance_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen,
+                                const uint32_t *d_k, uint32_t kMax, void *stream);
+int e2sar_hip_rows_clear_seen(e2sar_hip_ctx *ctx, const e2sar_hip_rows *w, const e2sar_hip_rows_seen *seen,
+                              uint64_t eventBase, void *stream);
 
 /* Which events are ready, decided on the device: the k that e2sar_hip_rows_advance takes,    */
 /* so that e2sar_hip_rows_reassemble -> e2sar_hip_rows_ready -> consumer ->                  */

@@ -21,10 +21,21 @@ timed beside `rows` instead of the two arena forms, one form per W:
                      consecutively; the window takes every W-th event and passes the rest over.
                      Reported with the time of `rows` and that time divided by W beside it.
 
+With --seen [pair|dup16|all] a window that survives duplicates (frag_bytes = the segmenter's payload
+per datagram) is timed beside the plain one instead of the two arena forms -- pair
+(the default): rows and rows_seen; dup16: rows_dup16 and rows_seen_dup16; all: the four in one
+process, where a form's time follows its place among them:
+
+  rows_seen          e2sar_hip_rows_clear_seen outside the clock, then one
+                     e2sar_hip_rows_reassemble_seen of the batch `rows` takes
+  rows_dup16,        the same two calls on that batch with every 16th datagram sent twice, the copy
+  rows_seen_dup16    straight behind the original; the plain window's result is then not the events
+                     (its curBytes pass the events' lengths), only its time is used
+
 Every form's output is compared with the events' source bytes once.
 
   python tools/rows_bench.py [--events 205] [--event-bytes 1048576] [--mtus 1500,9000]
-                             [--step W[,W...]] [--landing own|spread]
+                             [--step W[,W...]] [--landing own|spread] [--seen [MODE]]
                              [--reps 40] [--warmup 5] [--out FILE]
 Prints one JSON line (and writes it to --out).  Rates count payload bytes read + written once.
 """
@@ -109,15 +120,63 @@ def batch(ctx, args, mtu, src, torch, sar):
             name, form, owned = lattice(ctx, args, W, seg, src, host, (pk, ln, n), base, pitch, sar)
             forms[name] = form
             moved[name] = 2 * owned * B
+    if args.seen:
+        more, n_dup = seen_forms(ctx, args, seg, host, (pk, ln, n), base, pitch, n_events, win, torch, sar)
+        more["rows"] = forms["rows"]
+        forms = {name: more[name] for name in SEEN_FORMS[args.seen]}
+        moved.update({name: 2 * E * B for name in forms})
     us = ab_method.measure(forms, args)
     out = ab_method.summary(us, moved)
     out["datagrams"] = n
+    if args.seen:
+        out["datagrams_dup16"] = n_dup
+        for name, against in (("rows_seen", "rows"), ("rows_seen_dup16", "rows_dup16")):
+            if name not in out:
+                continue
+            out[name]["of_plain_median"] = round(out[name]["median_us"] / out[against]["median_us"], 3)
     if args.step and args.landing == "spread":
         for W in args.step:
             out[f"rows_spread{W}"]["rows_median_over_W_us"] = round(out["rows"]["median_us"] / W, 2)
             out[f"rows_spread{W}"]["of_rows_median"] = round(out[f"rows_spread{W}"]["median_us"] / out["rows"]["median_us"], 3)
     R.close()
     return out
+
+
+# --seen MODE: the forms of one process.  Two forms on one batch follow each other alike; with all four in one
+# process a form's time follows its place among them -- whose batch went through the caches before it
+SEEN_FORMS = {"pair": ("rows", "rows_seen"), "dup16": ("rows_dup16", "rows_seen_dup16"),
+              "all": ("rows", "rows_seen", "rows_dup16", "rows_seen_dup16")}
+
+
+def seen_forms(ctx, args, seg, host, whole, base, pitch, n_events, plain, torch, sar):
+    """The window with bits beside `plain`, and both on the batch with every 16th datagram twice:
+    -> ({form name: (fn, before)}, the datagrams of that batch)."""
+    E, B = args.events, args.event_bytes
+    pk, ln, n = whole
+    win = sar.RowWindow(ctx, [4321], n_events, pitch, base, with_lb_header=True, frag_bytes=seg.max_pld)
+    idx = torch.tensor([k for i in range(n) for k in ((i, i) if i % 16 == 0 else (i,))], dtype=torch.int64, device=pk.device)
+    n2 = idx.numel()
+    pk2 = pk.view(-1, seg.stride)[:n].index_select(0, idx).reshape(-1).contiguous()
+    ln2 = ln[:n].index_select(0, idx).contiguous()
+    forms = {
+        "rows_seen": (lambda: win.reassemble(pk, seg.stride, ln, n), lambda: win.clear(base)),
+        "rows_dup16": (lambda: plain.reassemble(pk2, seg.stride, ln2, n2), lambda: plain.clear(base)),
+        "rows_seen_dup16": (lambda: win.reassemble(pk2, seg.stride, ln2, n2), lambda: win.clear(base)),
+    }
+    for name, dup in (("rows_seen", 0), ("rows_seen_dup16", n2 - n)):
+        win.out.zero_()
+        win.clear(base)
+        forms[name][0]()
+        cells = win.parse_cells()[:, 0]
+        c, _ = win.parse_counts()
+        assert c[0] == E and c[1] == n and c[2] == E * B and c[11] == dup and not any(c[3:11]), (name, c)
+        got = win.out[:, 0, :B].cpu().numpy()
+        for i in range(E):
+            r = (base + i) & (n_events - 1)
+            assert cells[r]["flags"] == 1 and cells[r]["bytes"] == B, (name, i, cells[r])
+            assert np.array_equal(got[r], host[i]), (name, i)
+        assert int(np.unpackbits(win.parse_seen().view(np.uint8)).sum()) == n, name
+    return forms, n2
 
 
 def lattice(ctx, args, W, seg, src, host, whole, base, pitch, sar):
@@ -159,10 +218,14 @@ def main():
     ap.add_argument("--mtus", default="1500,9000")
     ap.add_argument("--step", default="", help="W[,W...]: time the window of rank 0 of W beside `rows`")
     ap.add_argument("--landing", choices=["own", "spread"], default="own")
+    ap.add_argument("--seen", nargs="?", const="pair", default=None, choices=sorted(SEEN_FORMS),
+                    help="time the window that survives duplicates beside `rows`: pair (default), dup16 or all")
     args = ap.parse_args()
     args.step = [int(w) for w in args.step.split(",") if w]
     if any(w < 2 for w in args.step):
         ap.error("--step takes values of at least 2")
+    if args.seen and args.step:
+        ap.error("--seen and --step are separate runs")
 
     import torch
     from e2sar_amd import sar, _capi
@@ -175,7 +238,7 @@ def main():
     g.manual_seed(1234)
     src = torch.randint(0, 256, (E, (B + 255) // 256 * 256), dtype=torch.uint8, device=dev, generator=g)
     result = {"tool": "rows_bench", "events": E, "event_bytes": B, "reps": args.reps,
-              "step": args.step, "landing": args.landing if args.step else None,
+              "step": args.step, "landing": args.landing if args.step else None, "seen": args.seen,
               "lib": os.path.basename(_capi.LIB_PATH), "device": torch.cuda.get_device_name(0), "mtu": {}}
     for mtu in (int(m) for m in args.mtus.split(",")):
         result["mtu"][str(mtu)] = batch(ctx, args, mtu, src, torch, sar)
